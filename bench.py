@@ -2,8 +2,18 @@
 """Benchmark of the MI355X kd-tree hot path: batched k=32 kNN self-queries over
 1e8 uniform periodic particles (BASELINE.json metric), plus build time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it generates the
+particles, builds the tree once, warms up, times the K steps and prints the
+line (value, ms_per_step, the per-kernel HIP-event times of those same steps).
+--dump-outputs DIR then writes a fixed, seeded sample of the last timed step's
+rows as DIR/<name>.npy, so two builds can be compared output for output.
+--full adds everything else: the timed rebuilds, the work-counter pass, the
+roofline lookups, the CPU baseline with its parity check, and at N > 1 the
+steps without the second round; --suite (which implies --full) the secondary
+runs.
 
 One step = one pass of the hot path over one batch: every particle queried
 for its k=32 nearest neighbours (query bucketing + radix sort + packet collect /
@@ -191,6 +201,14 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline figure: timed "
+                        "rebuilds, the work-counter pass, the roofline, the CPU baseline and "
+                        "its parity check (--no-cpu-baseline / --no-parity trim it), the "
+                        "N > 1 steps without the second round")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a fixed seeded sample of the last timed "
+                        "step's output rows to DIR/<name>.npy (float32 / float64, under 64 MB)")
     p.add_argument("--particles", dest="n", type=float, default=1e8,
                    help="particles: the total over all GPUs (strong scaling, default) or per "
                         "GPU (--scaling weak)")
@@ -211,7 +229,7 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-parity", action="store_true")
     p.add_argument("--suite", action="store_true",
-                   help="also measure SURVEY §8(d)'s secondary runs (independent uniform "
+                   help="--full plus SURVEY §8(d)'s secondary runs (independent uniform "
                         "queries, C3 radius count + CSR batch, log-normal kNN) into 'suite'")
     p.add_argument("--radius", type=float, default=0.01, help="C3 radius, units of L")
     p.add_argument("--deposit-grid", type=int, default=1024,
@@ -235,7 +253,9 @@ def parse():
     p.add_argument("--input-format", choices=("raw", "gadget"), default="raw",
                    help="gadget: a Gadget-2 snapshot (format 1/2, multi-file; N > 1 streams each "
                         "rank's slab unless --redistribute); the box is its BoxSize")
-    return p.parse_args()
+    args = p.parse_args()
+    args.full = args.full or args.suite  # the secondary runs check against the CPU legs
+    return args
 
 
 def log(*a):
@@ -381,6 +401,49 @@ def timed(fn, steps, hip):
         fn()
     hip.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_BYTES, DUMP_BLOCK_ROWS = 52_000_000, 1024  # k=32 rows as f32 + f64: 128 blocks, 51.4 MB
+
+
+def sample_blocks(rows, seed, bytes_per_row):
+    """The fixed sample of output rows --dump-outputs writes: blocks of
+    DUMP_BLOCK_ROWS consecutive rows, as many as DUMP_BYTES on disk hold, their
+    starts drawn once from `seed` (every row when the whole output fits).
+    Returns (starts, rows per block)."""
+    if rows * bytes_per_row <= DUMP_BYTES:
+        return np.zeros(1, np.int64), rows
+    nblk = max(1, DUMP_BYTES // (DUMP_BLOCK_ROWS * bytes_per_row))
+    rng = np.random.Generator(np.random.PCG64([seed, 0xD0]))
+    starts = np.sort(rng.choice(rows // DUMP_BLOCK_ROWS, size=nblk, replace=False))
+    return starts.astype(np.int64) * DUMP_BLOCK_ROWS, DUMP_BLOCK_ROWS
+
+
+def read_blocks(hip, dev, starts, blk):
+    """Rows [s, s + blk) of the device array for every s of starts, on the host."""
+    out = np.empty((len(starts) * blk,) + dev.shape[1:], dev.dtype)
+    row_bytes = dev.nbytes // max(dev.shape[0], 1)
+    for j, s in enumerate(starts):
+        hip.memcpy(out.ctypes.data + j * blk * row_bytes, dev.ptr + int(s) * row_bytes,
+                   blk * row_bytes, hip.D2H)
+    return out
+
+
+def dump_outputs(path, hip, arrays, rows, seed, rank, world):
+    """--dump-outputs: the sampled rows of each device array of `arrays` (name ->
+    (DeviceArray, dtype on disk)) as path/<name>.npy, plus the sampled row numbers as
+    rows.npy; at N > 1 every rank writes its own rows as <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    hip.synchronize()
+    per_row = 8 + sum(int(np.prod(dev.shape[1:])) * np.dtype(dtype).itemsize
+                      for dev, dtype in arrays.values())
+    starts, blk = sample_blocks(rows, seed, per_row)
+    tag = "" if world == 1 else f"_rank{rank}"
+    ids = (starts[:, None] + np.arange(blk, dtype=np.int64)[None, :]).reshape(-1)
+    np.save(os.path.join(path, f"rows{tag}.npy"), ids.astype(np.float64))
+    for name, (dev, dtype) in arrays.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"),
+                read_blocks(hip, dev, starts, blk).astype(dtype))
 
 
 def suite(args, capi, hip, tree, dev_pts, n, k, L, stream, od, oi):
@@ -689,6 +752,10 @@ def run_c5(args, rank, world, local_rank, dist, same_dev, barrier, allmax, allsu
 
     t_r = timed_max(radius_step)
     t_k = timed_max(kth_step)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hip, {"radius_count": (cnt, np.float64),
+                                              "kth_distance": (rk, np.float32)},
+                     own, args.seed, rank, world)
     # density estimates (host, from the last passes), in units of the mean density
     rho_bar = n_total / L ** 3
     c = cnt.numpy_head(own).astype(np.float64)
@@ -974,24 +1041,27 @@ def main():
             t.set_ids(dev_ptr=ds.ids.ptr, stream=stream.handle)
         return t
 
-    # build: one untimed (code-object load; also the process's first build,
-    # which pays the shape enumeration and the allocations the later builds
-    # reuse), then timed rebuilds of the same size
+    # build: the process's first build (code-object load, the shape
+    # enumeration and the allocations later builds reuse); a plain run keeps
+    # that tree, --full then times two rebuilds of the same size
     hip.synchronize()
     t0 = time.perf_counter()
-    build_tree().close()
+    tree = build_tree()
     hip.synchronize()
     build_ms_first = allmax((time.perf_counter() - t0) * 1e3)
-    build_ms = []
-    for _ in range(2):
-        hip.synchronize()
-        t0 = time.perf_counter()
-        tree = build_tree()
-        hip.synchronize()
-        build_ms.append((time.perf_counter() - t0) * 1e3)
-        if _ == 0:
-            tree.close()
-    build_ms = allmax(min(build_ms))
+    build_ms = None
+    if args.full:
+        tree.close()
+        build_ms = []
+        for _ in range(2):
+            hip.synchronize()
+            t0 = time.perf_counter()
+            tree = build_tree()
+            hip.synchronize()
+            build_ms.append((time.perf_counter() - t0) * 1e3)
+            if _ == 0:
+                tree.close()
+        build_ms = allmax(min(build_ms))
 
     # N > 1: two row buffers, so a step's second round overlaps the next step
     bufs = [(hip.DeviceArray((own, k), np.float32), hip.DeviceArray((own, k), np.uint32))
@@ -1057,14 +1127,15 @@ def main():
     drain()
     stream.synchronize()
     if ds is not None:
-        # the slab-local rows before the second round: how many reach past the halo
-        tree.query_device(dev_pts.ptr, own, k, od.ptr, oi.ptr, stream.handle)
-        stream.synchronize()
-        halo["rows_past_halo_before_second_round"] = int(
-            allsum(float(ds.violations(od.ptr, k, stream.handle))))
-        step()  # and resolved again, so the checked rows below are the exact ones
-        drain()
-        stream.synchronize()
+        if args.full:
+            # the slab-local rows before the second round: how many reach past the halo
+            tree.query_device(dev_pts.ptr, own, k, od.ptr, oi.ptr, stream.handle)
+            stream.synchronize()
+            halo["rows_past_halo_before_second_round"] = int(
+                allsum(float(ds.violations(od.ptr, k, stream.handle))))
+            step()  # and resolved again, so the checked rows below are the exact ones
+            drain()
+            stream.synchronize()
         halo.update({"h": ds.h, "local_points": n_local, "transport": ds.transport})
         for kk in sr_acc:
             sr_acc[kk] = 0
@@ -1097,26 +1168,35 @@ def main():
     elapsed_max = allmax(elapsed)
     own_total = int(allsum(float(own)))  # file inputs: slabs differ in size
 
-    # work counters of our own traversal (one extra, untimed pass)
-    capi.stats_enable(True)
-    counters["stats"] = True
-    step()
-    stream.synchronize()
-    st = capi.stats_read_all()
-    pts_scanned = st["pair_evals"]
-    capi.stats_enable(False)
-    counters["stats"] = False
-    drain()  # that step's second round: its rows are the exact ones read below
-    stream.synchronize()
-    od, oi = bufs[pipe["last"]]
+    if args.dump_outputs:
+        # the last timed step's rows, as KDTree.query returns them: distances
+        # (f32) and neighbour ids (u32, written as f64: exact)
+        dump_outputs(args.dump_outputs, hip, {"distances": (od, np.float32),
+                                              "indices": (oi, np.float64)},
+                     own, args.seed, rank, world)
+
+    st = None
+    if args.full:
+        # work counters of our own traversal (one extra, untimed pass)
+        capi.stats_enable(True)
+        counters["stats"] = True
+        step()
+        stream.synchronize()
+        st = capi.stats_read_all()
+        capi.stats_enable(False)
+        counters["stats"] = False
+        drain()  # that step's second round: its rows are the exact ones read below
+        stream.synchronize()
+        od, oi = bufs[pipe["last"]]
 
     gpu_d = gpu_i = None
     parity_rows = min(args.cpu_sample, own)
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         gpu_d = od.numpy_head(parity_rows)
         gpu_i = oi.numpy_head(parity_rows)
 
-    if ds is not None:
+    knn_only = knn_only_local = None
+    if ds is not None and args.full:
         # the same steps without the second round (rows then inexact, never
         # reported): what the round adds to a step, on the same (possibly
         # shared) device
@@ -1129,6 +1209,7 @@ def main():
         barrier()
         knn_only_local = (time.perf_counter() - t_k) / args.steps
         knn_only = allmax(knn_only_local * args.steps) / args.steps
+    if ds is not None:
         halo["second_round"] = {
             "transport": rows.transport,
             "rows_forwarded_per_step": allsum(float(sr_timed["rows_forwarded"])) / max(args.steps, 1),
@@ -1136,10 +1217,11 @@ def main():
             "max_hops": int(allmax(float(sr_timed["hops"]))),
             # overlapped with the next step's kNN (pipelined steps); the host's
             # time in it once the count is known (agreement over gloo, any
-            # forwarded rows), and the step time over the same steps without it
+            # forwarded rows), and (--full) the step time over the same steps
+            # without it
             "host_ms_per_step": allmax(sr_timed["host_s"]) / args.steps * 1e3,
-            "ms_per_step": (elapsed_max / args.steps - knn_only) * 1e3,
-            "knn_only_ms_per_step": knn_only * 1e3,
+            "ms_per_step": None if knn_only is None else (elapsed_max / args.steps - knn_only) * 1e3,
+            "knn_only_ms_per_step": None if knn_only is None else knn_only * 1e3,
         }
         counts = allgather_int(own)
         # every rank's own numbers beside the max-over-ranks step (VERDICT r05
@@ -1148,7 +1230,7 @@ def main():
             "step_ms": elapsed / args.steps * 1e3,
             "collect_ms_per_launch": col_ms / max(col_launches, 1),
             "select_ms_per_step": sel_ms / args.steps,
-            "knn_only_ms_per_step": knn_only_local * 1e3,
+            "knn_only_ms_per_step": None if knn_only_local is None else knn_only_local * 1e3,
             "second_round_host_ms_per_step": sr_timed["host_s"] / args.steps * 1e3,
             "own_particles": own, "local_points": n_local,
             "halo_transport": ds.transport, "second_round_transport": rows.transport},
@@ -1158,36 +1240,10 @@ def main():
     total_q = own_total * args.steps
     value = total_q / elapsed_max
     ms_per_step = elapsed_max / args.steps * 1e3
-    bq = bytes_per_query(k)
-    # dominant kernel: the collect kernel (knn_collect_grp_kernel), launched once
-    # per query batch (the candidate-column budget); achieved = algorithmic bytes
-    # of the queries one launch processes / that launch's average duration (HIP
-    # events on the launch stream)
-    col_launches = max(col_launches, 1)
-    col_avg_ms = col_ms / col_launches
-    q_per_launch = own * args.steps / col_launches
-    achieved = bq * q_per_launch / (col_avg_ms * 1e-3) / 1e9
-    # HBM bytes per collect launch from rocprofv3 PMC passes of THIS build: a
-    # committed profiles/rNN_pmc_knn.json (scripts/summarize_prof.py: FETCH_SIZE
-    # x2 (gfx950) + WRITE_SIZE, separate runs) whose recorded libnbkd.so SHA-256
-    # equals the loaded library's, for the same workload; else null
-    traffic, traffic_source = pmc_traffic(own, k, q_per_launch)
-    # the whole step's HBM bytes (every kernel of the query), same build, one GPU
-    step_traffic, step_source = pmc_step_traffic(own, k) if world == 1 else (None, None)
-    step_sec = elapsed_max / args.steps
-    useful = float(own_total) * k * 8 + 16.0 * (own_total if world == 1 else allsum(float(n_local))) \
-        + 16.0 * (tree.size if world == 1 else allsum(float(tree.size)))
-    step_ach = None if step_traffic is None else step_traffic / step_sec / 1e9
-    peak = HBM_PEAK_GBS
-    basis = None
-    if world > 1:
-        ent, src = pmc_slab(args, world, k)
-        sr = slab_roofline(ent, src, world, bq, q_per_launch, own, col_avg_ms, step_sec,
-                           allsum, allmax)
-        traffic, step_traffic = sr["traffic"], sr["step_traffic"]
-        traffic_source = step_source = sr["source"]
-        achieved, col_avg_ms, step_ach = sr["work_achieved"], sr["kernel_ms"], sr["step_achieved"]
-        peak, basis = sr["peak"], sr["basis"]
+    # --full: a collective at N > 1 (every rank calls it, before rank 0 alone goes on)
+    roofline = roofline_of_run(args, world, own, own_total, n_local, tree.size, k, value,
+                               elapsed_max / args.steps, col_ms, col_launches,
+                               allsum, allmax) if args.full else None
     if rank != 0:
         return
     extra = None
@@ -1195,7 +1251,7 @@ def main():
         extra = suite(args, capi, hip, tree, dev_pts, n, k, L, stream, od, oi)
     cpu = None
     parity = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline(points, k, args.leafsize, L, parity_rows, gpu_d, gpu_i,
                                    threads=args.cpu_threads)
     out = {
@@ -1210,6 +1266,7 @@ def main():
         "scaling": args.scaling,
         "vs_baseline": None,
         "dtype": "f32",
+        "full": bool(args.full),
         "data": (f"file: {os.path.basename(args.input)} ({args.input_format}); self-queries"
                  if args.input else
                  "synthetic: numpy PCG64 uniform [0,L)^3, L=1, float32; self-queries"),
@@ -1229,33 +1286,84 @@ def main():
         "halo": halo,
         "build_ms": build_ms,
         "build_ms_first": build_ms_first,
-        "roofline": roofline_entry(
-            traffic, traffic_source, col_avg_ms, achieved, peak=peak,
-            kernel="knn_collect_grp_kernel<periodic> (nbodyhpc_amd/csrc/knn_collect.hip)",
-            step_work_frac=value * bq / (HBM_PEAK_GBS * 1e9 * world),
-            launches_per_step=col_launches / args.steps, queries_per_launch=q_per_launch,
-            bytes_per_query=bq, peak_per_gpu=HBM_PEAK_GBS, traffic_basis=basis,
-            # the whole pipeline (bucketing, sort, collect, select, retries):
-            # PMC HBM bytes of one step / the step's wall time
-            step_traffic=step_traffic, step_traffic_source=step_source,
-            step_achieved=step_ach,
-            step_frac=None if step_ach is None else step_ach / peak,
-            # the bytes a step cannot avoid: the k-column rows
-            # written (f32 + u32), the packed points read once (16 B) and the
-            # node table (16 B per node); the step's PMC traffic over this is
-            # the step's waste factor
-            useful_bytes=useful,
-            useful_frac_of_step_traffic=None if step_traffic is None else useful / step_traffic,
-            useful_achieved=useful / step_sec / 1e9),
+        # per-kernel HIP-event times of the timed steps themselves
         "breakdown_ms_per_step": {
             "self_order": self_ms / args.steps, "leaf_key": key_ms / args.steps,
             "sort": sort_ms / args.steps, "knn": knn_ms / args.steps, "knn_collect": col_ms / args.steps,
             "knn_select": sel_ms / args.steps, "outside_box_check": oob_ms / args.steps,
             "retry": (rt_ms + rto_ms) / args.steps, "fallback": fb_ms / args.steps,
         },
+    }
+    if args.dump_outputs:
+        out["outputs_dir"] = args.dump_outputs
+    if args.full:
+        out.update(full_fields(roofline, st, own, cpu, parity))
+    if extra is not None:
+        out["suite"] = extra
+    print(json.dumps(out), flush=True)
+
+
+def roofline_of_run(args, world, own, own_total, n_local, tree_size, k, value, step_sec,
+                    col_ms, col_launches, allsum, allmax):
+    """--full: the line's `roofline` object from the timed steps' collect-kernel
+    events and the committed PMC summaries of this very library build."""
+    bq = bytes_per_query(k)
+    # dominant kernel: the collect kernel (knn_collect_grp_kernel), launched once
+    # per query batch (the candidate-column budget); achieved = algorithmic bytes
+    # of the queries one launch processes / that launch's average duration (HIP
+    # events on the launch stream)
+    col_launches = max(col_launches, 1)
+    col_avg_ms = col_ms / col_launches
+    q_per_launch = own * args.steps / col_launches
+    achieved = bq * q_per_launch / (col_avg_ms * 1e-3) / 1e9
+    # HBM bytes per collect launch from rocprofv3 PMC passes of THIS build: a
+    # committed profiles/rNN_pmc_knn.json (scripts/summarize_prof.py: FETCH_SIZE
+    # x2 (gfx950) + WRITE_SIZE, separate runs) whose recorded libnbkd.so SHA-256
+    # equals the loaded library's, for the same workload; else null
+    traffic, traffic_source = pmc_traffic(own, k, q_per_launch)
+    # the whole step's HBM bytes (every kernel of the query), same build, one GPU
+    step_traffic, step_source = pmc_step_traffic(own, k) if world == 1 else (None, None)
+    useful = float(own_total) * k * 8 + 16.0 * (own_total if world == 1 else allsum(float(n_local))) \
+        + 16.0 * (tree_size if world == 1 else allsum(float(tree_size)))
+    step_ach = None if step_traffic is None else step_traffic / step_sec / 1e9
+    peak = HBM_PEAK_GBS
+    basis = None
+    if world > 1:
+        ent, src = pmc_slab(args, world, k)
+        sr = slab_roofline(ent, src, world, bq, q_per_launch, own, col_avg_ms, step_sec,
+                           allsum, allmax)
+        traffic, step_traffic = sr["traffic"], sr["step_traffic"]
+        traffic_source = step_source = sr["source"]
+        achieved, col_avg_ms, step_ach = sr["work_achieved"], sr["kernel_ms"], sr["step_achieved"]
+        peak, basis = sr["peak"], sr["basis"]
+    return roofline_entry(
+        traffic, traffic_source, col_avg_ms, achieved, peak=peak,
+        kernel="knn_collect_grp_kernel<periodic> (nbodyhpc_amd/csrc/knn_collect.hip)",
+        step_work_frac=value * bq / (HBM_PEAK_GBS * 1e9 * world),
+        launches_per_step=col_launches / args.steps, queries_per_launch=q_per_launch,
+        bytes_per_query=bq, peak_per_gpu=HBM_PEAK_GBS, traffic_basis=basis,
+        # the whole pipeline (bucketing, sort, collect, select, retries):
+        # PMC HBM bytes of one step / the step's wall time
+        step_traffic=step_traffic, step_traffic_source=step_source,
+        step_achieved=step_ach,
+        step_frac=None if step_ach is None else step_ach / peak,
+        # the bytes a step cannot avoid (VERDICT r05 #1): the k-column rows
+        # written (f32 + u32), the packed points read once (16 B) and the
+        # node table (16 B per node); the step's PMC traffic over this is
+        # the step's waste factor
+        useful_bytes=useful,
+        useful_frac_of_step_traffic=None if step_traffic is None else useful / step_traffic,
+        useful_achieved=useful / step_sec / 1e9)
+
+
+def full_fields(roofline, st, own, cpu, parity):
+    """--full: the line's fields beside the headline ones (roofline, the
+    work-counter pass `st`, the CPU baseline and its parity check)."""
+    return {
+        "roofline": roofline,
         # one packet = 64 queries walking the tree together: node visits are
         # per packet walk; distance evaluations are per (query, point) pair
-        "traversal_per_query": {"distance_evals": pts_scanned / own,
+        "traversal_per_query": {"distance_evals": st["pair_evals"] / own,
                                 "candidates": st["candidates"] / own},
         "traversal_per_packet": {kk: st[kk] / max(st["packets"], 1)
                                  for kk in ("node_visits", "leaves_reached", "sparse_iters",
@@ -1275,9 +1383,6 @@ def main():
         "cpu_host": None if cpu is None else cpu["host"],
         "parity_vs_cpu": parity,
     }
-    if extra is not None:
-        out["suite"] = extra
-    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

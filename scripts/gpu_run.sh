@@ -6,8 +6,8 @@
 # Steps run in the order given; the first that fails ends the call (every GPU
 # step has its own time limit).  Everything lands under gpurun_out/$TAG/.
 #   tests     pytest -m gpu, then smoke()
-#   bench     the default bench line (N = 1, the driver's command)
-#   suite     bench.py --suite (SURVEY §8(d)'s secondary runs)
+#   bench     the bench line with --full (N = 1): baseline, parity, roofline
+#   suite     bench.py --full --suite (SURVEY §8(d)'s secondary runs)
 #   trace     rocprofv3 --kernel-trace --stats of a short bench
 #   pmc       FETCH_SIZE / WRITE_SIZE passes (separate runs) of collect / select
 #             and of the C3 radius count, and the SQ / TCC sets of both
@@ -16,7 +16,7 @@
 #             8:weak:1.25e8"): rank 0's slab of the N-GPU bench alone on this GPU
 #   rehearse  N > 1 bench lines with every rank on this GPU (NBKD_BENCH_SAME_DEVICE=1)
 #   ab        scripts/gpu_ab.sh with LIBS / BALL_LIBS / ARGS / ROUNDS
-#   final     smoke() + the default bench line
+#   final     smoke() + the bench line with --full
 #   probe     each command of PROBE ("cmd1; cmd2; ..."), 600 s each, into probe.log
 #   summarize summarize_prof.py / summarize_step.py on the box (profiles/<tag>_*,
 #             copied to $O/profiles), so a later bench / suite step matches them
@@ -31,7 +31,7 @@ TAG=${TAG:-run}
 O=gpurun_out/$TAG
 mkdir -p $O
 sha256sum nbodyhpc_amd/lib/libnbkd.so > $O/lib.sha256
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
 BR="python3 scripts/ball_run.py"
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 SQ2="SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
@@ -70,14 +70,14 @@ step_tests() {
 }
 step_bench() {
   say bench
-  timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err
   local rc=$?
   tail -c 1500 $O/bench.json
   return $rc
 }
 step_suite() {
   say suite
-  timeout -k 10 900 python3 bench.py --suite > $O/suite.json 2> $O/suite.err
+  timeout -k 10 900 python3 bench.py --full --suite > $O/suite.json 2> $O/suite.err
 }
 step_trace() {
   say trace
@@ -120,7 +120,7 @@ step_rehearse() {
   local w
   for w in ${REHEARSE:-2 4}; do
     say "rehearse n$w"
-    NBKD_BENCH_SAME_DEVICE=1 timeout -k 10 900 python3 bench.py --gpus $w --steps 3 --warmup 1 \
+    NBKD_BENCH_SAME_DEVICE=1 timeout -k 10 900 python3 bench.py --full --gpus $w --steps 3 --warmup 1 \
       --no-cpu-baseline > $O/rehearse_n$w.json 2> $O/rehearse_n$w.err || return $?
     tail -c 2500 $O/rehearse_n$w.json
   done
@@ -133,7 +133,7 @@ step_final() {
   say final
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" \
     > $O/final_smoke.log 2>&1 \
-    && timeout -k 10 600 python3 bench.py > $O/final_bench.json 2> $O/final_bench.err
+    && timeout -k 10 600 python3 bench.py --full > $O/final_bench.json 2> $O/final_bench.err
   local rc=$?
   tail -2 $O/final_smoke.log; tail -c 1500 $O/final_bench.json
   return $rc

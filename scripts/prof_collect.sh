@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/${TAG:-pc}
 mkdir -p $O
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity ${BENCH_ARGS}"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-parity ${BENCH_ARGS}"
 declare -A P
 P[sq1]="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 P[sq2]="SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"

@@ -134,7 +134,7 @@ def main():
             "lib_sha256": lib_sha,
             "kernel": (b or {}).get("roofline", {}).get("kernel", regex),
             "command": f"rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-include-regex {regex} -- "
-                       "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity",
+                       "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity",
             "n_particles": cfg.get("n_particles_per_gpu", 100_000_000), "k": cfg.get("k", 32),
             "queries_per_launch": (b or {}).get("roofline", {}).get("queries_per_launch"),
             "dispatches": [len(fv), len(wv)],

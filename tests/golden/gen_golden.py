@@ -23,8 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from oracle.oracle import Reference  # noqa: E402
-from tests.golden.inputs import (edge_cases, g1_inputs, g2_inputs, g3_inputs, g4_inputs,  # noqa: E402
-                                 g5_inputs, g7_inputs, node_shape, sha)
+from tests.golden.inputs import (augment_inputs, edge_cases, g1_inputs, g2_inputs,  # noqa: E402
+                                 g3_inputs, g4_inputs, g5_inputs, g7_inputs, node_shape, sha)
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -55,9 +55,43 @@ def g7(R):
     np.savez_compressed(os.path.join(OUT, "g7_scale_nodes.npz"), **out)
 
 
+def g8():
+    """G8: the reference's augment_vertices_periodic over augment_inputs()
+    (gen_golden.py --only g8): per case the image positions and the ball each
+    belongs to, in the reference's order; the radius column only repeats the
+    ball's radius, so it is checked here and not stored."""
+    from oracle.oracle import VertexReference
+    ref = VertexReference()
+    out = {}
+    for j, (xyz, w, r, box) in enumerate(augment_inputs()):
+        aug = ref.augment(xyz, w, r, box)
+        ball = aug[:, 3].astype(np.uint16)
+        assert np.array_equal(ball.astype(np.float32), aug[:, 3])
+        assert np.array_equal(aug[:, 4].view(np.uint32), r[ball].view(np.uint32))
+        out[f"sha_{j}"] = np.array(sha(xyz, r))
+        out[f"pos_{j}"] = np.ascontiguousarray(aug[:, :3])
+        out[f"ball_{j}"] = ball
+    np.savez_compressed(os.path.join(OUT, "g8_augment.npz"), **out)
+
+
+def cites():
+    """The reference's file names and line counts (gen_golden.py --only cites),
+    which tests/test_citations.py resolves `file:line` citations against."""
+    import json
+
+    from tests.test_citations import LINES, walk_reference
+    with open(LINES, "w") as f:
+        json.dump(walk_reference(), f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
 def main():
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+    if only in ("g8", "cites"):
+        {"g8": g8, "cites": cites}[only]()
+        return
     R = Reference()
-    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "g7":
+    if only == "g7":
         g7(R)
         return
 
@@ -121,6 +155,8 @@ def main():
         out["box_error"] = np.array(1)
     np.savez_compressed(os.path.join(OUT, "g6_edges.npz"), **out)
     g7(R)
+    g8()
+    cites()
     print("fixtures written to", OUT)
 
 

@@ -124,3 +124,21 @@ def edge_cases():
     # a single point
     out["single"] = (np.array([[0.25, 0.5, 0.75]], np.float32), uniform(5, 16), 2, 128, 1.0)
     return out
+
+
+def augment_inputs():
+    """G8, the periodic-image cases: [(xyz, weight, radius, box)].  Balls
+    straddling one, two or three faces, radii wider than half the box, zero,
+    negative and infinite radii, points exactly on the faces, a non-periodic
+    axis (box <= 0); the ball index travels as the weight."""
+    rng = np.random.default_rng(12)
+    n = 3000
+    out = []
+    for box in ((1.0, 1.0, 1.0), (2.0, 1.5, -1.0), (1.0, -1.0, 0.5)):
+        per = np.asarray(box, np.float32)
+        ext = np.where(per > 0, per, 1.0)
+        xyz = (rng.uniform(-0.05, 1.05, (n, 3)) * ext).astype(np.float32)
+        xyz[:50] = np.where(per > 0, per, 1.0) * rng.integers(0, 2, (50, 3))  # on the faces
+        r = rng.choice(np.array([0.0, 0.01, 0.1, 0.3, 0.7, -0.1, np.inf], np.float32), n)
+        out.append((xyz, np.arange(n, dtype=np.float32), r, box))
+    return out

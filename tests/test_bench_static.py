@@ -132,6 +132,24 @@ def _bench_module():
     return mod
 
 
+def test_dump_sample_is_fixed_and_under_64_mb():
+    """--dump-outputs at the headline shape (1e8 rows, k = 32: f32 distances,
+    ids as f64, the row numbers as f64): the sampled row blocks depend on the
+    seed alone, lie inside the output, do not overlap and stay under 64 MB on
+    disk; an output that fits is written whole."""
+    bench = _bench_module()
+    n, per_row = 100_000_000, 8 + 32 * 4 + 32 * 8
+    starts, blk = bench.sample_blocks(n, 20261015, per_row)
+    again, _ = bench.sample_blocks(n, 20261015, per_row)
+    other, _ = bench.sample_blocks(n, 7, per_row)
+    assert (starts == again).all() and not (starts == other).all()
+    assert blk == bench.DUMP_BLOCK_ROWS and (starts % blk == 0).all()
+    assert len(set(starts.tolist())) == len(starts) and starts.min() >= 0 and starts.max() + blk <= n
+    assert 32_000_000 < len(starts) * blk * per_row <= 64_000_000
+    starts, blk = bench.sample_blocks(1000, 20261015, per_row)
+    assert starts.tolist() == [0] and blk == 1000
+
+
 def test_n_gt_1_roofline_from_per_rank_slab_profiles(tmp_path, monkeypatch):
     """an N > 1 line finds the slab profile of its own build
     and decomposition (library SHA, world, scaling, --particles, k, leafsize,

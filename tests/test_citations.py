@@ -1,14 +1,17 @@
 """Every `file:line` citation of a reference source in this repo resolves:
-the cited lines exist in that file under /root/reference (VERDICT r03 found
-kdtree_impl.hpp citations past the end of the 275-line file).  Reads the
-reference as text only; skipped where it is absent (the GPU box)."""
+the cited lines exist in that file of the reference (VERDICT r03 found
+kdtree_impl.hpp citations past the end of the 275-line file).  The reference's
+file names and line counts are recorded in tests/golden/reference_lines.json,
+so the check runs everywhere; where the reference itself is present the
+record is compared with it first."""
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
+LINES = os.path.join(ROOT, "tests", "golden", "reference_lines.json")
+CITED_EXT = (".cpp", ".hpp", ".h", ".py", ".asm", ".pyi", ".txt", ".vert", ".frag")
 SCAN = ["oracle", "nbodyhpc_amd", "include", "tests", "nbodyhpc", "DESIGN.md", "INTEGRATION.md",
         "bench.py", "README.md", "BASELINE.md", "__graft_entry__.py"]
 EXT = (".py", ".c", ".cpp", ".h", ".hpp", ".hip", ".md", ".pyi")
@@ -20,29 +23,38 @@ MORE = re.compile(r"\s*(?:,|;|and|&)?\s*:(\d+)(?:-(\d+))?")
 BARE = re.compile(r"\(\s*:(\d+)(?:-(\d+))?(?:\s*,\s*:(\d+)(?:-(\d+))?)*\s*\)")
 
 
-def _ref_files():
-    by_name, by_path = {}, {}
-    for d, _, fs in os.walk(REF):
+def walk_reference(ref=REF):
+    """{path relative to the reference: its line count} of every file a
+    citation can name (tests/golden/gen_golden.py --only cites records it)."""
+    out = {}
+    for d, _, fs in os.walk(ref):
         if "/.git" in d:
             continue
         for f in fs:
-            p = os.path.join(d, f)
-            rel = os.path.relpath(p, REF)
-            by_path[rel] = p
-            by_name.setdefault(f, []).append(p)
+            if f.endswith(CITED_EXT):
+                p = os.path.join(d, f)
+                with open(p, "rb") as fh:
+                    out[os.path.relpath(p, ref)] = fh.read().count(b"\n") + 1
+    return out
+
+
+def _ref_files():
+    """The recorded index (names and line counts only), so the check runs where
+    the reference is absent; where it is present the index must equal it."""
+    with open(LINES) as f:
+        by_path = json.load(f)
+    if os.path.isdir(os.path.join(REF, "kdtree")):
+        assert by_path == walk_reference(), "tests/golden/reference_lines.json is stale"
+    by_name = {}
+    for rel in by_path:
+        by_name.setdefault(os.path.basename(rel), []).append(rel)
     return by_name, by_path
 
 
-def _lines(path, cache={}):
-    if path not in cache:
-        with open(path, "rb") as f:
-            cache[path] = f.read().count(b"\n") + 1
-    return cache[path]
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "kdtree")), reason="reference absent")
 def test_reference_citations_resolve():
-    by_name, by_path = _ref_files()
+    by_name, lines = _ref_files()
+    by_path = {rel: rel for rel in lines}
+    _lines = lines.__getitem__
     bad, checked = [], 0
     for top in SCAN:
         p0 = os.path.join(ROOT, top)
@@ -55,7 +67,8 @@ def test_reference_citations_resolve():
             for m in CITE.finditer(txt):
                 name = m.group(1)
                 cands = [by_path[name]] if name in by_path else [
-                    p for p in by_name.get(os.path.basename(name), []) if p.endswith(name)]
+                    p for p in by_name.get(os.path.basename(name), [])
+                    if os.path.join(REF, p).endswith(name)]
                 if not cands:
                     continue  # not a reference file
                 ranges = [(int(m.group(2)), int(m.group(3) or m.group(2)))]

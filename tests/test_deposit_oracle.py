@@ -180,7 +180,7 @@ def test_rasterizer_argument_errors():
     assert _normalize_period((1.0, 2.0, 3.0), (4.0, 5.0)) == (4.0, 5.0, -1.0)
 
 
-def test_periodic_images_pinned_to_reference_augment():
+def test_periodic_images_pinned_to_reference_augment(golden):
     """The deposit oracle's periodic images (and so nbkd_deposit's, which is
     checked against that oracle) equal the reference's own
     augment_vertices_periodic (rasterization/src/cpp/vertex_utilities.cpp:13-42,
@@ -191,21 +191,24 @@ def test_periodic_images_pinned_to_reference_augment():
     import os
 
     from oracle.oracle import VERTEX_REF_PATH, Oracle, VertexReference
+    from tests.golden.inputs import augment_inputs, sha
 
-    if not os.path.exists(VERTEX_REF_PATH) and not os.path.isdir("/root/reference/rasterization"):
-        pytest.skip("oracle/_ref/libvertex_ref.so not built here")
-    ref = VertexReference()
+    # the reference's output is recorded (tests/golden/g8_augment.npz, written
+    # by gen_golden.py --only g8 from the compiled reference); where the compiled
+    # reference is present, the record must equal what it returns now
+    live = os.path.exists(VERTEX_REF_PATH) or os.path.isdir("/root/reference/rasterization")
+    ref = VertexReference() if live else None
+    gold = golden("g8_augment")
     orc = Oracle()
-    rng = np.random.default_rng(12)
-    n = 3000
-    for box in ((1.0, 1.0, 1.0), (2.0, 1.5, -1.0), (1.0, -1.0, 0.5)):
-        per = np.asarray(box, np.float32)
-        ext = np.where(per > 0, per, 1.0)
-        xyz = (rng.uniform(-0.05, 1.05, (n, 3)) * ext).astype(np.float32)
-        xyz[:50] = np.where(per > 0, per, 1.0) * rng.integers(0, 2, (50, 3))  # on the faces
-        r = rng.choice(np.array([0.0, 0.01, 0.1, 0.3, 0.7, -0.1, np.inf], np.float32), n)
-        w = np.arange(n, dtype=np.float32)  # the ball index travels as the weight
-        aug = ref.augment(xyz, w, r, box)
+    for j, (xyz, w, r, box) in enumerate(augment_inputs()):
+        n = len(r)
+        assert sha(xyz, r) == str(gold[f"sha_{j}"])
+        # (x, y, z, ball index): the ball index travels as the weight
+        aug = np.column_stack([gold[f"pos_{j}"], gold[f"ball_{j}"].astype(np.float32)])
+        if ref is not None:
+            now = ref.augment(xyz, w, r, box)
+            assert np.array_equal(now[:, :4].view(np.uint32), aug.view(np.uint32))
+            assert np.array_equal(now[:, 4].view(np.uint32), r[now[:, 3].astype(int)].view(np.uint32))
         mine = orc.deposit_images(xyz, r, box)
         by_ball = [[] for _ in range(n)]
         for v in aug:

@@ -331,6 +331,49 @@ def test_bench_c5_line_small(gpu, oracle, monkeypatch, capsys):
     assert abs(got - dens.mean()) < 1e-6 * dens.mean()
 
 
+def test_bench_plain_line_and_dump_outputs(gpu, oracle, monkeypatch, capsys, tmp_path):
+    """bench.py in-process at a small size: a plain run times --steps steps and
+    prints the headline fields only (no CPU baseline, work counters or
+    roofline), and --dump-outputs writes the last step's rows, for a seeded
+    sample of row blocks, as float32 / float64 .npy that equal the oracle's rows
+    for the same particles; the same arguments sample the same rows."""
+    import json
+    import sys
+
+    import bench
+    from tests.parity import assert_knn_equal
+
+    n, k = 100_000, 8
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2_000_000)  # so that 1e5 rows are sampled
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--particles", str(n), "--k", str(k),
+                                      "--leafsize", "32", "--steps", "3", "--warmup", "1",
+                                      "--dump-outputs", str(tmp_path)])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line["full"] is False and line["steps"] == 3 and line["dtype"] == "f32"
+    assert line["unit"] == "queries/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for kk in ("cpu_baseline", "parity_vs_cpu", "roofline", "traversal_per_query", "suite"):
+        assert kk not in line
+    rows = np.load(tmp_path / "rows.npy")
+    d = np.load(tmp_path / "distances.npy")
+    i = np.load(tmp_path / "indices.npy")
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["distances.npy", "indices.npy", "rows.npy"]
+    assert d.dtype == np.float32 and i.dtype == np.float64 and rows.dtype == np.float64
+    assert d.shape == i.shape == (len(rows), k) and 0 < len(rows) < n
+    assert d.nbytes + i.nbytes + rows.nbytes <= 2_000_000
+    seed = bench.parse().seed
+    starts, blk = bench.sample_blocks(n, seed, 8 + 12 * k)
+    want = (starts[:, None] + np.arange(blk)[None, :]).reshape(-1)
+    assert np.array_equal(rows, want) and len(np.unique(rows)) == len(rows)
+    pts = bench.gen_uniform(n, seed, 1.0)
+    q = pts[rows.astype(np.int64)]
+    rd, ri = oracle.tree(pts, 32, 1.0).query(q, k, workers=8)
+    assert np.array_equal(i, i.astype(np.uint32))
+    assert_knn_equal(d, i.astype(np.uint32), rd, ri, pts, q, 1.0)
+
+
 def _deposit_worker(rank, world, port, n_per, grid, outdir):
     from nbodyhpc_amd import hip
 
