@@ -141,6 +141,31 @@ nbkd_status nbkd_query_ball_count(const nbkd_tree *tree, const float *q, uint64_
                                   uint32_t *out_count, uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): the radius count for nr radii in one tree
+ * walk: the pair counts DD(r) of a correlation function, cumulative neighbour
+ * profiles, densities at several scales (scipy's count_neighbors(other, r)
+ * with an array r).  radii is (nr,) float32, host memory, ascending (equal
+ * neighbours allowed), each finite and >= 0, 1 <= nr <= NBKD_MAX_RADII.  The
+ * count of query i at radius j is the number of points with d2 <= r[j]*r[j]
+ * (float32, the tree's metric): column j of out_counts equals
+ * nbkd_query_ball_count(q, r[j]) bit for bit.  Counts are cumulative in j;
+ * per-bin counts are their differences.
+ *   out_counts  (m, nr) row-major uint32, host or device memory
+ *               (NBKD_OUTPUT_DEVICE), or NULL
+ *   out_total   (nr,) uint64, always host memory, or NULL: the sum of column j
+ *               over the m queries (exact: integer atomics on the device)
+ * At least one of the two must be given.  With out_total the call returns when
+ * both outputs are complete; with out_total == NULL and device queries and
+ * counts it returns once the work is enqueued, as nbkd_query_ball_count does.
+ * Host arrays stream in batches (see above); the totals accumulate over them.
+ * m == 0 is NBKD_OK with out_total zeroed.
+ */
+#define NBKD_MAX_RADII 32
+nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t m,
+                                 const float *radii, int32_t nr, uint32_t *out_counts,
+                                 uint64_t *out_total, uint32_t flags, void *stream);
+
+/*
  * NEW: neighbour lists within r in CSR form.  out_offsets is (m+1,) uint64
  * (always host memory); out_idx receives offsets[m] original point indices,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row

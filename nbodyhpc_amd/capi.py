@@ -45,6 +45,7 @@ _PROTOS = {
     "nbkd_query_knn": (_i32, [_c_p, _c_p, _u64, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_kth": (_i32, [_c_p, _c_p, _u64, _i32, _c_p, _u32, _c_p]),
     "nbkd_query_ball_count": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _u32, _c_p]),
+    "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
     "nbkd_tree_info": (_i32, [_c_p, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
@@ -225,6 +226,30 @@ class Tree:
     def ball_count_device(self, q_ptr, m, r, out_ptr, stream=None):
         _check(lib().nbkd_query_ball_count(self.h, q_ptr, int(m), float(r), out_ptr,
                                            NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+
+    def ball_hist(self, q, radii, counts=True, total=True):
+        """nbkd_query_ball_hist of host queries: (cumulative counts (m, nr) uint32
+        or None, column sums (nr,) uint64 or None) for the ascending radii."""
+        q = _host_f32(q).reshape(-1, 3)
+        r = _host_f32(radii).reshape(-1)
+        m, nr = q.shape[0], r.shape[0]
+        c = np.empty((m, nr), np.uint32) if counts else None
+        t = np.empty(nr, np.uint64) if total else None
+        _check(lib().nbkd_query_ball_hist(self.h, q.ctypes.data, m, r.ctypes.data, nr,
+                                          c.ctypes.data if counts else None,
+                                          t.ctypes.data if total else None, 0, None))
+        return c, t
+
+    def ball_hist_device(self, q_ptr, m, radii, out_ptr, total=True, stream=None):
+        """Device queries, device counts ((m, nr) uint32; out_ptr None: totals
+        only); returns the (nr,) uint64 totals (the call then waits for them)
+        or None (the call returns once enqueued)."""
+        r = _host_f32(radii).reshape(-1)
+        t = np.empty(r.shape[0], np.uint64) if total else None
+        _check(lib().nbkd_query_ball_hist(self.h, q_ptr, int(m), r.ctypes.data, r.shape[0],
+                                          out_ptr, t.ctypes.data if total else None,
+                                          NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+        return t
 
     def ball_csr(self, q, r, sorted=False):
         """CSR radius query of host queries: (offsets (m + 1,) uint64, ids);

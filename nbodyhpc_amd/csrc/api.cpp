@@ -603,6 +603,42 @@ nbkd_status nbkd_query_ball_count(const nbkd_tree *tree, const float *q, uint64_
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t m,
+                                 const float *radii, int32_t nr, uint32_t *out_counts,
+                                 uint64_t *out_total, uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q || !radii) {
+        set_error("nbkd_query_ball_hist: NULL argument (tree, q or radii)");
+        return NBKD_EINVAL;
+    }
+    if (!out_counts && !out_total) {
+        set_error("nbkd_query_ball_hist: out_counts and out_total are both NULL");
+        return NBKD_EINVAL;
+    }
+    if (nr < 1 || nr > NBKD_MAX_RADII) {
+        set_error("nbkd_query_ball_hist: the number of radii must be in [1, " +
+                  std::to_string(NBKD_MAX_RADII) + "], got " + std::to_string(nr));
+        return NBKD_EINVAL;
+    }
+    for (int32_t j = 0; j < nr; ++j) {
+        if (!(radii[j] >= 0.0f) || !(radii[j] <= FLT_MAX)) {
+            set_error("nbkd_query_ball_hist: radius " + std::to_string(j) +
+                      " is NaN, infinite or negative");
+            return NBKD_EINVAL;
+        }
+        if (j > 0 && radii[j] < radii[j - 1]) {
+            set_error("nbkd_query_ball_hist: the radii must be ascending (radius " +
+                      std::to_string(j) + " is below radius " + std::to_string(j - 1) + ")");
+            return NBKD_EINVAL;
+        }
+    }
+    DeviceGuard g(tree->t.device);
+    return query_ball_hist(tree->t, q, m, radii, nr, out_counts, out_total, flags,
+                           (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_query_ball_csr(const nbkd_tree *tree, const float *q, uint64_t m, float r,
                                 uint64_t *out_offsets, uint32_t *out_idx, uint64_t capacity,
                                 uint32_t flags, void *stream) {

@@ -36,24 +36,9 @@ constexpr int TB = 256;
 constexpr int WPB = TB / 64;
 constexpr int CHUNK = 64; // one staged chunk per leaf up to leafsize 64
 
-struct PadLeaves {
-    uint32_t id[NBKD_PAD_LEAVES];
-};
-
 struct alignas(16) BallLds {
     float4 p4[CHUNK]; // the staged points: x, y, z, original id bits (Tree::p4)
 };
-
-// upper bound of the f32 d2 of point_d2_fast over every point of the box: per
-// axis |fl(x - q)| is monotone in x, so it is at most the larger end value; the
-// periodic minimum image only lowers it
-template <bool PER>
-__device__ __forceinline__ float box_ub2(float qx, float qy, float qz, const float b[6]) {
-    const float ux = fmaxf(fabsf(b[0] - qx), fabsf(b[1] - qx));
-    const float uy = fmaxf(fabsf(b[2] - qy), fabsf(b[3] - qy));
-    const float uz = fmaxf(fabsf(b[4] - qz), fabsf(b[5] - qz));
-    return (ux * ux + uy * uy) + uz * uz;
-}
 
 // The CSR fill (nbkd_query_ball_csr's second pass): 64-query packets, the
 // packet walk, and at each leaf the lanes whose ball contains the tight box

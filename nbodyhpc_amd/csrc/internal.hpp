@@ -22,7 +22,7 @@ namespace nbkd {
 enum WsSlot {
     WS_Q = 0, WS_KEYS, WS_KEYS2, WS_ORDER, WS_TMP, WS_HIST, WS_SUMS, WS_OUTD, WS_OUTI,
     WS_COUNT, WS_OFF, WS_IDX, WS_STATS, WS_LIST, WS_LT, WS_TG, WS_CAND, WS_CCOUNT,
-    WS_LIST2, WS_RSORT, WS_KTHD, WS_KTHI, WS_KB, WS_ANCH, WS_PAIR,
+    WS_LIST2, WS_RSORT, WS_KTHD, WS_KTHI, WS_KB, WS_ANCH, WS_PAIR, WS_HTOT,
     // host-buffer pipeline (query.hip host_pipeline): two slots of queries and
     // of up to two result arrays
     WS_HQ0, WS_HQ1, WS_HO00, WS_HO01, WS_HO10, WS_HO11, WS_NSLOTS
@@ -397,6 +397,22 @@ void launch_ball_outside(const Tree &t, const float *q, const uint32_t *list, ui
                          float r2, uint32_t *out_count, uint32_t *fill,
                          const uint64_t *row_offsets, uint32_t *out_idx, hipStream_t s);
 
+// ball_hist.hip: the radius histogram.  thr.t[0 .. nr) = the ascending squared
+// radii (passed to the kernels by value); out_counts = (m, nr) cumulative
+// counts per query or nullptr, totals = nr counters the column sums are added
+// to or nullptr.  Periodic queries outside [0, L]^3 are skipped by the packet
+// kernel and answered by the second launch (list length in device memory).
+struct HistThr {
+    float t[NBKD_MAX_RADII];
+};
+void launch_ball_hist(const Tree &t, const float *q, const uint32_t *order, uint32_t m,
+                      const HistThr &thr, int nr, uint32_t *out_counts,
+                      unsigned long long *totals, hipStream_t s);
+void launch_ball_hist_outside_dev(const Tree &t, const float *q, const uint32_t *list,
+                                  const uint32_t *nout, const HistThr &thr, int nr,
+                                  uint32_t *out_counts, unsigned long long *totals,
+                                  hipStream_t s);
+
 // per-row sort of a CSR batch (row offsets `off`, nrows + 1 entries, device):
 // rows of up to csr_sort_row_cap() ids in place; longer rows are appended to
 // long_rows (count in *nlong, zeroed by the caller) for the caller to sort
@@ -414,6 +430,10 @@ nbkd_status query_ball_count(const Tree &t, const float *q, uint64_t m, float r,
                              uint32_t *out_count, uint32_t flags, hipStream_t s);
 nbkd_status query_ball_csr(const Tree &t, const float *q, uint64_t m, float r, uint64_t *offsets,
                            uint32_t *out_idx, uint64_t capacity, uint32_t flags, hipStream_t s);
+// radii: nr ascending, finite, non-negative (checked by the caller, api.cpp)
+nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const float *radii, int nr,
+                            uint32_t *out_counts, uint64_t *out_total, uint32_t flags,
+                            hipStream_t s);
 
 // query.hip: LSD radix sort of (key, value) pairs by the low nbits of the keys,
 // ping-ponging (k0, v0) <-> (k1, v1); *vout = the buffer holding the sorted values

@@ -118,6 +118,17 @@ __device__ __forceinline__ float box_lb2(float qx, float qy, float qz, const flo
     return r;
 }
 
+// upper bound of the f32 d2 of point_d2_fast over every point of the box: per
+// axis |fl(x - q)| is monotone in x, so it is at most the larger end value; the
+// periodic minimum image only lowers it
+template <bool PER>
+__device__ __forceinline__ float box_ub2(float qx, float qy, float qz, const float b[6]) {
+    const float ux = fmaxf(fabsf(b[0] - qx), fabsf(b[1] - qx));
+    const float uy = fmaxf(fabsf(b[2] - qy), fabsf(b[3] - qy));
+    const float uz = fmaxf(fabsf(b[4] - qz), fabsf(b[5] - qz));
+    return (ux * ux + uy * uy) + uz * uz;
+}
+
 // Every point p of the box lies within L/2 of q on every axis: then the
 // periodic per-axis minimum min(d^2, (L - |d|)^2) (the reference's
 // min(d^2, (d-L)^2, (d+L)^2), kdtree.hpp:72-84) is d^2 itself with the same

@@ -103,6 +103,12 @@ __device__ __forceinline__ void knn_fail_check(bool valid, bool seeded, uint32_t
 }
 
 
+// the ids of the leaves that hold padding points (Tree::pad_leaves), passed to
+// the radius kernels by value
+struct PadLeaves {
+    uint32_t id[NBKD_PAD_LEAVES];
+};
+
 // ------------------------------------------------------------------ packet walk
 // The wave's depth-first walk (knn_collect.hip, ball.hip).  The macros expect in
 // scope: lane, qx/qy/qz, the bound kth, L, cnodes, the walk state node / nd (its

@@ -6,7 +6,8 @@
 // k=1, workers=1)), same properties (n = padded count, size = node count,
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
-// (query_ball_count / query_ball_csr) and export() for parity tests.
+// (query_ball_count / query_ball_csr / query_ball_hist) and export() for
+// parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
 // kdtree/src/cpp/kdtree.cpp:116).  Queries release the GIL, may be called from
@@ -161,6 +162,38 @@ class PyKDTree {
         return out;
     }
 
+    // the radius count for nr ascending radii in one walk (nbkd_query_ball_hist):
+    // (total uint64 (nr,), cumulative counts uint32 (m, nr) or None)
+    py::tuple query_ball_hist(farray points, farray radii, bool per_point) {
+        check_shape(points);
+        if (radii.ndim() != 1) throw std::runtime_error("radii must be a 1D array");
+        const py::ssize_t m = points.shape(0), nr = radii.shape(0);
+        if (nr < 1 || nr > NBKD_MAX_RADII)
+            throw std::runtime_error("the number of radii must be in [1, " +
+                                     std::to_string(NBKD_MAX_RADII) + "]");
+        py::array_t<uint64_t> total(nr);
+        py::object counts = py::none();
+        uint32_t *c = nullptr;
+        if (per_point) {
+            py::array_t<uint32_t> arr({m, nr});
+            c = arr.mutable_data();
+            counts = arr;
+        }
+        const float *q = points.data(), *r = radii.data();
+        uint64_t *tp = total.mutable_data();
+        // (m == 0: no array to point at; the library only zeroes the totals)
+        const float dummy[3] = {0.0f, 0.0f, 0.0f};
+        if (m == 0) q = dummy;
+        nbkd_status st;
+        Interruptible intr;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_query_ball_hist(h_, q, (uint64_t)m, r, (int32_t)nr, c, tp, 0u, nullptr);
+        }
+        intr.finish(st);
+        return py::make_tuple(total, counts);
+    }
+
     // rows sorted ascending on the device unless sorted=false (NBKD_SORTED);
     // both passes stream in batches and poll Ctrl-C between them
     std::pair<py::array_t<uint64_t>, py::array_t<uint32_t>> query_ball_csr(farray points, float r,
@@ -219,6 +252,8 @@ PYBIND11_MODULE(_impl, m) {
              py::arg("workers") = 1)
         .def("query_kth", &PyKDTree::query_kth, py::arg("points"), py::arg("k"))
         .def("query_ball_count", &PyKDTree::query_ball_count, py::arg("points"), py::arg("r"))
+        .def("query_ball_hist", &PyKDTree::query_ball_hist, py::arg("points"), py::arg("radii"),
+             py::arg("per_point") = false)
         .def("query_ball_csr", &PyKDTree::query_ball_csr, py::arg("points"), py::arg("r"),
              py::arg("sorted") = true)
         .def("export", &PyKDTree::export_tree)

@@ -1821,6 +1821,87 @@ nbkd_status query_ball_count(const Tree &t, const float *q, uint64_t m, float r,
                          }, s);
 }
 
+// the radius histogram of m device queries: rows into the device array
+// out_counts (or nullptr), column sums added to the device counters tot (or
+// nullptr)
+static nbkd_status hist_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
+                               const HistThr &thr, int nr, uint32_t *out_counts,
+                               unsigned long long *tot, uint32_t flags, hipStream_t s) {
+    if (m == 0) return NBKD_OK;
+    const uint32_t mm = (uint32_t)m;
+    const float *dq = nullptr;
+    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
+    if (rc) return rc;
+    uint32_t *ord = nullptr;
+    rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
+                                    : sort_queries(t, ws, dq, mm, ord, s);
+    if (rc) return rc;
+    // periodic queries outside [0, L]^3: listed (the length stays in device
+    // memory), every point tested for them
+    uint32_t *list = nullptr;
+    if (t.periodic) {
+        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
+        if (!list) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
+        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
+    }
+    TimedScope ts("ball_hist", s);
+    launch_ball_hist(t, dq, ord, mm, thr, nr, out_counts, tot, s);
+    if (list) launch_ball_hist_outside_dev(t, dq, list, list + mm, thr, nr, out_counts, tot, s);
+    NBKD_HIP(hipGetLastError());
+    return NBKD_OK;
+}
+
+nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const float *radii, int nr,
+                            uint32_t *out_counts, uint64_t *out_total, uint32_t flags,
+                            hipStream_t s) {
+    if (m >= (1ull << 32)) {
+        set_error("more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (out_total) std::fill(out_total, out_total + nr, (uint64_t)0);
+    if (m == 0) return NBKD_OK;
+    // the thresholds, ball_common's expression per radius; they travel to the
+    // kernels by value (no host-to-device copy whose source could go away)
+    HistThr thr;
+    for (int j = 0; j < NBKD_MAX_RADII; ++j) {
+        const float r = radii[std::min(j, nr - 1)];
+        thr.t[j] = r * r;
+    }
+    Workspace &ws = acquire_ws(t);
+    WsCall call(ws, s, std::adopt_lock);
+    NBKD_HIP(call.err);
+    unsigned long long *tot = nullptr;
+    if (out_total) {
+        tot = (unsigned long long *)ws.get(WS_HTOT, NBKD_MAX_RADII * 8, s);
+        if (!tot) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemsetAsync(tot, 0, NBKD_MAX_RADII * 8, s));
+    }
+    // no rows wanted: nothing leaves the device but the totals
+    if (!out_counts) flags |= NBKD_OUTPUT_DEVICE;
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    nbkd_status rc;
+    if ((flags & dev_io) == dev_io) {
+        rc = hist_common(t, ws, q, m, thr, nr, out_counts, tot, flags, s);
+    } else {
+        const size_t ob[1] = {(size_t)nr * 4};
+        void *const outs[1] = {out_counts};
+        rc = host_pipeline(ws, q, m, flags, out_counts ? 1 : 0, ob, outs, 40,
+                           [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
+                               return hist_common(t, ws, dq, nb, thr, nr,
+                                                  out_counts ? (uint32_t *)o[0] : nullptr, tot,
+                                                  flags | dev_io, st);
+                           }, s);
+    }
+    if (rc) return rc;
+    if (out_total) {
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
+        NBKD_HIP(hipMemcpyAsync(out_total, tot, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
+        NBKD_HIP(hipStreamSynchronize(s));
+    }
+    return NBKD_OK;
+}
+
 namespace {
 
 // The CSR fill of one batch: nb device queries, their rows at the device

@@ -8,7 +8,8 @@ the C ABI in include/nbkd.h.  There is no CPU fallback: without the built
 extension or without a GPU the constructor raises.
 
 Additions (no reference counterpart): ``query_ball`` (scipy-style radius
-query, count or index lists), ``density`` (local number density from the k-th
+query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
+many radii in one tree walk), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
 no pickle inside) and pickling.  A restored tree is rebuilt on the GPU from
@@ -111,6 +112,55 @@ class KDTree(cKDTree):
         for i, row in enumerate(np.split(idx, off[1:-1].astype(np.int64)) if m else ()):
             rows[i] = row
         return rows.reshape(out_shape)
+
+    def count_neighbors(self, points: np.ndarray, r, cumulative: bool = True,
+                        per_point: bool = False):
+        """Neighbour counts at many radii in one tree walk (scipy's
+        ``count_neighbors(other, r)`` with an array ``r``).
+
+        r : a scalar or a 1-D ascending array of up to 32 radii (each finite
+            and >= 0; equal neighbours allowed).  The count at radius r[j] is
+            the number of tree points with d2 <= r[j]*r[j] in float32, the
+            value ``query_ball(points, r[j], return_length=True)`` gives.
+        per_point=False -> uint64 totals over all queries, shape (nr,) (a
+            scalar r: a Python int).
+        per_point=True -> uint32 counts, shape points.shape[:-1] + (nr,) (a
+            scalar r: points.shape[:-1]).
+        cumulative=False -> first differences along the radius axis: counts
+            per bin (r[j-1], r[j]], the first bin kept as it is.
+        """
+        scalar = np.ndim(r) == 0
+        radii = np.atleast_1d(np.asarray(r, dtype=np.float32))
+        if radii.ndim != 1:
+            raise ValueError("r must be a scalar or a 1-D array of radii")
+        if radii.size == 0:
+            raise ValueError("r is empty: at least one radius is needed")
+        if radii.size > 32:
+            raise ValueError(f"r holds {radii.size} radii: at most 32 per call")
+        if not np.all(np.isfinite(radii)) or np.any(radii < 0):
+            raise ValueError("every radius must be finite and >= 0")
+        if np.any(radii[1:] < radii[:-1]):
+            raise ValueError("r must be ascending (non-decreasing)")
+        points, shape = _flatten(points)
+        out_shape = tuple(shape[:-1]) if shape is not None else (np.asarray(points).shape[0],)
+        total, counts = super().query_ball_hist(points, radii, bool(per_point))
+        res = counts.reshape(out_shape + (radii.size,)) if per_point else total
+        if not cumulative:
+            res = np.diff(res, axis=-1, prepend=res.dtype.type(0))
+        if scalar:
+            return res[..., 0] if per_point else int(res[0])
+        return res
+
+    def pair_counts(self, r):
+        """Auto pair counts DD(<= r) of the tree's own points, cumulative in r:
+        unordered pairs i < j with d2 <= r*r, self pairs removed.  Coincident
+        distinct particles (d2 = 0) still count as pairs.  ``r`` as in
+        ``count_neighbors``; returns uint64 (nr,) (a scalar r: a Python int)."""
+        n = self._n_input
+        total = self.count_neighbors(self.points(), r)
+        if np.ndim(r) == 0:
+            return (total - n) // 2
+        return (total - np.uint64(n)) // np.uint64(2)
 
     def kth_distance(self, points: np.ndarray, k: int):
         """Distance to the k-th nearest neighbour of each point: column k-1 of
