@@ -166,6 +166,35 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
                                  uint64_t *out_total, uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): friends-of-friends groups of the tree's own
+ * points, the halo finder's first step.  Points i and j are friends iff
+ * d2(i, j) <= b*b in float32, with d2 the tree's metric and b*b formed in
+ * float32: exactly the predicate of nbkd_query_ball_count
+ * (((dx^2 + dy^2) + dz^2), per-axis minimum image on a periodic tree).  Groups
+ * are the connected components of the friendship graph; a point without a
+ * friend is a group of one.  b == 0 is valid (only coincident points link); b
+ * NaN, infinite or negative is NBKD_EINVAL.
+ *   out_label   (n,) uint32, required: out_label[i] = the smallest input row of
+ *               i's group.  Labels are input rows 0..n-1 (the build's
+ *               permutation), also after nbkd_set_ids replaced the ids.  The
+ *               labelling is canonical: two calls give arrays equal under ==.
+ *   out_size    (n,) uint32 or NULL: out_size[l] = the member count of the
+ *               group whose label is l, 0 at every row that is not a label
+ *               (sum = n, number of nonzeros = *out_ngroups).
+ *   out_ngroups host memory, or NULL: the number of groups.
+ * Padding points are in no group; no element >= n is written.
+ * NBKD_OUTPUT_DEVICE: out_label and out_size are device pointers; with
+ * out_ngroups == NULL the call then returns once the work is enqueued, as
+ * nbkd_query_ball_count does, otherwise when every output is complete.
+ * One tree walk with bound b*b over the points in tree order joins friends in
+ * a lock-free union-find (integer atomics only).  Scratch: 8 bytes per point
+ * of the call's workspace (two uint32 per tree position), plus staging of the
+ * host outputs.
+ */
+nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32_t *out_size,
+                     uint64_t *out_ngroups, uint32_t flags, void *stream);
+
+/*
  * NEW: neighbour lists within r in CSR form.  out_offsets is (m+1,) uint64
  * (always host memory); out_idx receives offsets[m] original point indices,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row

@@ -48,6 +48,7 @@ _PROTOS = {
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
+    "nbkd_fof": (_i32, [_c_p, ctypes.c_float, _c_p, _c_p, ctypes.POINTER(_u64), _u32, _c_p]),
     "nbkd_tree_info": (_i32, [_c_p, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                               ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_float),
                               ctypes.POINTER(_i32)]),
@@ -154,6 +155,7 @@ class Tree:
         _check(st)
         self.h = h
         self._keep = None
+        self.npoints = int(count)  # the caller's point count (self.n is the padded one)
         n8, nn, per, box, dev = _u64(), _u64(), _i32(), ctypes.c_float(), _i32()
         _check(L.nbkd_tree_info(h, ctypes.byref(n8), ctypes.byref(nn), ctypes.byref(per),
                                 ctypes.byref(box), ctypes.byref(dev)))
@@ -250,6 +252,22 @@ class Tree:
                                           out_ptr, t.ctypes.data if total else None,
                                           NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
         return t
+
+    def fof(self, b, sizes=True):
+        """nbkd_fof into host arrays: (labels (n,) uint32 = the smallest input
+        row of each point's group, sizes (n,) uint32 or None, ngroups)."""
+        n = self.npoints
+        lab = np.empty(n, np.uint32)
+        siz = np.empty(n, np.uint32) if sizes else None
+        ng = _u64()
+        _check(lib().nbkd_fof(self.h, float(b), lab.ctypes.data,
+                              siz.ctypes.data if sizes else None, ctypes.byref(ng), 0, None))
+        return lab, siz, ng.value
+
+    def fof_device(self, b, labels_ptr, sizes_ptr=None, stream=None):
+        """nbkd_fof into device arrays ((n,) uint32 each); returns once enqueued."""
+        _check(lib().nbkd_fof(self.h, float(b), labels_ptr, sizes_ptr, None,
+                              NBKD_OUTPUT_DEVICE, stream))
 
     def ball_csr(self, q, r, sorted=False):
         """CSR radius query of host queries: (offsets (m + 1,) uint64, ids);

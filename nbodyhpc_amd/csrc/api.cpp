@@ -639,6 +639,23 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32_t *out_size,
+                     uint64_t *out_ngroups, uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !out_label) {
+        set_error("nbkd_fof: NULL argument (tree or out_label)");
+        return NBKD_EINVAL;
+    }
+    if (!(b >= 0.0f) || !(b <= FLT_MAX)) {
+        set_error("nbkd_fof: the linking length is NaN, infinite or negative");
+        return NBKD_EINVAL;
+    }
+    DeviceGuard g(tree->t.device);
+    return fof(tree->t, b, out_label, out_size, out_ngroups, flags, (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_query_ball_csr(const nbkd_tree *tree, const float *q, uint64_t m, float r,
                                 uint64_t *out_offsets, uint32_t *out_idx, uint64_t capacity,
                                 uint32_t flags, void *stream) {

@@ -435,6 +435,11 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
                             uint32_t *out_counts, uint64_t *out_total, uint32_t flags,
                             hipStream_t s);
 
+// fof.hip: friends-of-friends groups of the tree's own points (b finite and
+// >= 0, out_label != nullptr: checked by the caller, api.cpp)
+nbkd_status fof(const Tree &t, float b, uint32_t *out_label, uint32_t *out_size,
+                uint64_t *out_ngroups, uint32_t flags, hipStream_t s);
+
 // query.hip: LSD radix sort of (key, value) pairs by the low nbits of the keys,
 // ping-ponging (k0, v0) <-> (k1, v1); *vout = the buffer holding the sorted values
 nbkd_status sort_pairs(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,

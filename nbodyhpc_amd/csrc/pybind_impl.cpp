@@ -76,6 +76,7 @@ class PyKDTree {
     float box_ = 0.0f;
     int device_ = 0;
     uint64_t n8_ = 0, nodes_ = 0;
+    uint64_t n_in_ = 0; // the caller's point count (n8_ is the padded one)
 
   public:
     PyKDTree(farray points, int leaf_size, int /*max_threads*/, std::optional<float> box_size,
@@ -91,6 +92,7 @@ class PyKDTree {
             st = nbkd_build(ptr, n, leaf_size, periodic_ ? 1 : 0, box_, device, 0u, nullptr, &h_);
         }
         check(st);
+        n_in_ = n;
         int32_t dev = 0;
         check(nbkd_tree_info(h_, &n8_, &nodes_, nullptr, nullptr, &dev));
         device_ = dev;
@@ -194,6 +196,21 @@ class PyKDTree {
         return py::make_tuple(total, counts);
     }
 
+    // friends-of-friends groups of the tree's points (nbkd_fof): (labels uint32
+    // (N,) = the smallest input row of each point's group, sizes uint32 (N,) =
+    // the member count at each label, 0 elsewhere)
+    std::pair<py::array_t<uint32_t>, py::array_t<uint32_t>> fof_labels(float b) {
+        py::array_t<uint32_t> labels((py::ssize_t)n_in_), sizes((py::ssize_t)n_in_);
+        uint32_t *l = labels.mutable_data(), *z = sizes.mutable_data();
+        nbkd_status st;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_fof(h_, b, l, z, nullptr, 0u, nullptr);
+        }
+        check(st);
+        return {labels, sizes};
+    }
+
     // rows sorted ascending on the device unless sorted=false (NBKD_SORTED);
     // both passes stream in batches and poll Ctrl-C between them
     std::pair<py::array_t<uint64_t>, py::array_t<uint32_t>> query_ball_csr(farray points, float r,
@@ -256,6 +273,7 @@ PYBIND11_MODULE(_impl, m) {
              py::arg("per_point") = false)
         .def("query_ball_csr", &PyKDTree::query_ball_csr, py::arg("points"), py::arg("r"),
              py::arg("sorted") = true)
+        .def("fof_labels", &PyKDTree::fof_labels, py::arg("b"))
         .def("export", &PyKDTree::export_tree)
         .def_property_readonly("n", &PyKDTree::num_points)
         .def_property_readonly("size", &PyKDTree::num_nodes)

@@ -9,7 +9,8 @@ extension or without a GPU the constructor raises.
 
 Additions (no reference counterpart): ``query_ball`` (scipy-style radius
 query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
-many radii in one tree walk), ``density`` (local number density from the k-th
+many radii in one tree walk), ``fof`` / ``fof_labels`` (friends-of-friends
+groups of the tree's points), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
 no pickle inside) and pickling.  A restored tree is rebuilt on the GPU from
@@ -161,6 +162,31 @@ class KDTree(cKDTree):
         if np.ndim(r) == 0:
             return (total - n) // 2
         return (total - np.uint64(n)) // np.uint64(2)
+
+    def fof(self, linking_length: float, min_members: int = 1, return_sizes: bool = False):
+        """Friends-of-friends groups of the tree's own points: two points are
+        friends when d2 <= linking_length**2 in float32 (the ``query_ball``
+        predicate, periodic on a periodic tree), groups are the connected
+        components.
+
+        Returns ``group``, int64 (N,): groups are numbered 0..G-1 by descending
+        size, ties by the smaller first member (input row); points of groups
+        with fewer than ``min_members`` members get -1.  With
+        return_sizes=True also ``sizes``, int64 (G,), the member counts in
+        that numbering.  ``fof_labels(b)`` gives the raw (labels, sizes) pair:
+        the smallest input row of each point's group and the member count at
+        each label.
+        """
+        labels, sizes = super().fof_labels(float(linking_length))
+        heads = np.flatnonzero(sizes >= max(int(min_members), 1))  # ascending labels
+        order = np.argsort(-sizes[heads].astype(np.int64), kind="stable")
+        heads = heads[order]
+        number = np.full(labels.shape[0], -1, np.int64)
+        number[heads] = np.arange(heads.shape[0], dtype=np.int64)
+        group = number[labels]
+        if return_sizes:
+            return group, sizes[heads].astype(np.int64)
+        return group
 
     def kth_distance(self, points: np.ndarray, k: int):
         """Distance to the k-th nearest neighbour of each point: column k-1 of
