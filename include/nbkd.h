@@ -195,6 +195,55 @@ nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32
                      uint64_t *out_ngroups, uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): kernel-weighted sums over each query's own
+ * ball, the gather form of SPH (rho_i = sigma / h_i^3 * sum_j m_j K(d_ij / h_i))
+ * and, with several value channels, field interpolation at arbitrary points.
+ *   q          (m, 3) float32
+ *   h          (m,) float32: query i's own radius, on the same side as q
+ *              (both host, or both device with NBKD_INPUT_DEVICE)
+ *   values     (n, nv) row-major float32 on the same side as q, indexed by input
+ *              row (the build's permutation, also after nbkd_set_ids), or NULL:
+ *              weight 1, nv must then be 1.  1 <= nv <= NBKD_MAX_VALUES.
+ *   out_sum    (m, nv) float32 or NULL;  out_count (m,) uint32 or NULL; at least
+ *              one; both host, or both device with NBKD_OUTPUT_DEVICE
+ * Point j is a neighbour of query i iff d2(i, j) <= h_i*h_i in float32 (the
+ * product formed in float32; a product that overflows counts as FLT_MAX):
+ * nbkd_query_ball_count's predicate with r = h_i, so with every h_i = r
+ * out_count equals nbkd_query_ball_count(q, r) bit for bit.
+ * out_sum[i, c] = sum_j values[j, c] * K(u_ij), every step in float32 without
+ * fused multiply-adds: inv_i = 1.0f / h_i (0 when h_i == 0),
+ * u = fminf(sqrtf(d2) * inv_i, 1.0f), and
+ *   NBKD_KERNEL_TOPHAT    K = 1
+ *   NBKD_KERNEL_CUBIC     u <= 1/2: (1 - 6*(u*u)) + 6*((u*u)*u)
+ *                         u >  1/2: w = 1 - u; 2*((w*w)*w)
+ *   NBKD_KERNEL_WENDLAND  w = 1 - u; w2 = w*w; (w2*w2)*(1 + 4*u)
+ * The sum is un-normalised: sigma / h^3 belongs to the caller (sigma = 3/(4 pi),
+ * 8/pi, 21/(2 pi) for the three kernels).  A query whose h_i is NaN, infinite
+ * or negative has an empty ball (sum 0, count 0); h_i == 0 reaches coincident
+ * points only, with u = 0.
+ * Deterministic: there are no floating-point atomics; each (query, channel) is
+ * summed by one lane into one float32 accumulator in the tree's traversal
+ * order (a periodic query outside [0, L]^3 by a fixed-order reduction over all
+ * points), so two identical calls give arrays that are equal under ==.  A call
+ * whose queries are the tree's build array (the self-order path) and one with
+ * other queries may differ in the last bits of out_sum, never in out_count.
+ * NBKD_EINVAL before any device call: NULL tree, q or h; both outputs NULL; nv
+ * out of range; values == NULL with nv != 1; an unknown kernel; m >= 2^32.
+ * m == 0 is NBKD_OK.  With device inputs and outputs the call returns once the
+ * work is enqueued, as nbkd_query_ball_count does.  Host arrays stream in
+ * batches (see above); values are uploaded once per call.  Scratch: 4 nv bytes
+ * per point of the call's workspace (the values in tree order).
+ */
+#define NBKD_KERNEL_TOPHAT   0   /* K(u) = 1                                   */
+#define NBKD_KERNEL_CUBIC    1   /* K(u) = 1 - 6u^2 + 6u^3 (u <= 1/2), 2(1-u)^3 */
+#define NBKD_KERNEL_WENDLAND 2   /* K(u) = (1-u)^4 (1 + 4u)   (Wendland C2)     */
+#define NBKD_MAX_VALUES 4
+nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t m,
+                                const float *h, const float *values, int32_t nv,
+                                int32_t kernel, float *out_sum, uint32_t *out_count,
+                                uint32_t flags, void *stream);
+
+/*
  * NEW: neighbour lists within r in CSR form.  out_offsets is (m+1,) uint64
  * (always host memory); out_idx receives offsets[m] original point indices,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row

@@ -21,6 +21,9 @@ NBKD_OUTPUT_DEVICE = 0x2
 NBKD_ACCUMULATE = 0x4
 NBKD_SQUARED = 0x8
 NBKD_SORTED = 0x10
+# nbkd_query_ball_sum kernels and channel limit
+KERNEL_TOPHAT, KERNEL_CUBIC, KERNEL_WENDLAND = 0, 1, 2
+NBKD_MAX_VALUES = 4
 
 NODE_DTYPE = np.dtype([("dim", "<i4"), ("split", "<f4"), ("left", "<u4"), ("right", "<u4")])
 
@@ -46,6 +49,8 @@ _PROTOS = {
     "nbkd_query_kth": (_i32, [_c_p, _c_p, _u64, _i32, _c_p, _u32, _c_p]),
     "nbkd_query_ball_count": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _u32, _c_p]),
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
+    "nbkd_query_ball_sum": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _u32,
+                                   _c_p]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
     "nbkd_fof": (_i32, [_c_p, ctypes.c_float, _c_p, _c_p, ctypes.POINTER(_u64), _u32, _c_p]),
@@ -252,6 +257,39 @@ class Tree:
                                           out_ptr, t.ctypes.data if total else None,
                                           NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
         return t
+
+    def ball_sum(self, q, h, values=None, kernel=1, count=False):
+        """nbkd_query_ball_sum of host arrays: the raw float32 sums, (m,) without
+        values or for 1-D values, else (m, nv); with count=True the pair (sums,
+        counts (m,) uint32).  h: one radius per query; values: (n,) or (n, nv)
+        by input row; kernel: KERNEL_TOPHAT / KERNEL_CUBIC / KERNEL_WENDLAND."""
+        q = _host_f32(q).reshape(-1, 3)
+        m = q.shape[0]
+        hh = _host_f32(h).reshape(-1)
+        if hh.shape[0] != m:
+            raise ValueError("h must hold one radius per query")
+        v, nv = None, 1
+        if values is not None:
+            v = _host_f32(values)
+            if v.ndim not in (1, 2) or v.shape[0] != self.npoints:
+                raise ValueError("values must be (n,) or (n, nv) with n the tree's point count")
+            nv = 1 if v.ndim == 1 else v.shape[1]
+        flat = v is None or v.ndim == 1
+        s = np.empty(m if flat else (m, nv), np.float32)
+        c = np.empty(m, np.uint32) if count else None
+        _check(lib().nbkd_query_ball_sum(self.h, q.ctypes.data, m, hh.ctypes.data,
+                                         None if v is None else v.ctypes.data, int(nv),
+                                         int(kernel), s.ctypes.data,
+                                         c.ctypes.data if count else None, 0, None))
+        return (s, c) if count else s
+
+    def ball_sum_device(self, q_ptr, m, h_ptr, values_ptr, nv, kernel, sum_ptr, count_ptr=None,
+                        stream=None):
+        """Device queries, radii, values ((n, nv) or None) and outputs ((m, nv)
+        float32 sums and / or (m,) uint32 counts); returns once enqueued."""
+        _check(lib().nbkd_query_ball_sum(self.h, q_ptr, int(m), h_ptr, values_ptr, int(nv),
+                                         int(kernel), sum_ptr, count_ptr,
+                                         NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
 
     def fof(self, b, sizes=True):
         """nbkd_fof into host arrays: (labels (n,) uint32 = the smallest input

@@ -639,6 +639,46 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t m,
+                                const float *h, const float *values, int32_t nv,
+                                int32_t kernel, float *out_sum, uint32_t *out_count,
+                                uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q || !h) {
+        set_error("nbkd_query_ball_sum: NULL argument (tree, q or h)");
+        return NBKD_EINVAL;
+    }
+    if (!out_sum && !out_count) {
+        set_error("nbkd_query_ball_sum: out_sum and out_count are both NULL");
+        return NBKD_EINVAL;
+    }
+    if (nv < 1 || nv > NBKD_MAX_VALUES) {
+        set_error("nbkd_query_ball_sum: the number of value channels must be in [1, " +
+                  std::to_string(NBKD_MAX_VALUES) + "], got " + std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    if (!values && nv != 1) {
+        set_error("nbkd_query_ball_sum: values == NULL (weight 1) needs nv == 1, got " +
+                  std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    if (kernel != NBKD_KERNEL_TOPHAT && kernel != NBKD_KERNEL_CUBIC &&
+        kernel != NBKD_KERNEL_WENDLAND) {
+        set_error("nbkd_query_ball_sum: unknown kernel " + std::to_string(kernel));
+        return NBKD_EINVAL;
+    }
+    if (m >= (1ull << 32)) {
+        set_error("more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) return NBKD_OK;
+    DeviceGuard g(tree->t.device);
+    return query_ball_sum(tree->t, q, m, h, values, nv, kernel, out_sum, out_count, flags,
+                          (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32_t *out_size,
                      uint64_t *out_ngroups, uint32_t flags, void *stream) {
     NBKD_GUARD_BEGIN

@@ -23,6 +23,9 @@ enum WsSlot {
     WS_Q = 0, WS_KEYS, WS_KEYS2, WS_ORDER, WS_TMP, WS_HIST, WS_SUMS, WS_OUTD, WS_OUTI,
     WS_COUNT, WS_OFF, WS_IDX, WS_STATS, WS_LIST, WS_LT, WS_TG, WS_CAND, WS_CCOUNT,
     WS_LIST2, WS_RSORT, WS_KTHD, WS_KTHI, WS_KB, WS_ANCH, WS_PAIR, WS_HTOT,
+    // nbkd_query_ball_sum: the values in tree order, the uploaded host values,
+    // a host batch's radii
+    WS_VT, WS_VALS, WS_HRAD,
     // host-buffer pipeline (query.hip host_pipeline): two slots of queries and
     // of up to two result arrays
     WS_HQ0, WS_HQ1, WS_HO00, WS_HO01, WS_HO10, WS_HO11, WS_NSLOTS
@@ -413,6 +416,22 @@ void launch_ball_hist_outside_dev(const Tree &t, const float *q, const uint32_t 
                                   uint32_t *out_counts, unsigned long long *totals,
                                   hipStream_t s);
 
+// ball_sum.hip: kernel-weighted sums over per-query balls (nbkd_query_ball_sum).
+// vt[p, c] = values[row(p), c] for tree positions p < n8 (values == nullptr: 1;
+// padding positions: 0), row(p) from the build's permutation
+void launch_ball_sum_gather(const Tree &t, const float *values, int nv, float *vt, hipStream_t s);
+// m kd-ordered device queries with radii h (indexed by query id like q);
+// out_sum (m, nv) and out_count (m,) device arrays, either may be nullptr.
+// Periodic queries outside [0, L]^3 are skipped by the packet kernel and
+// answered by the second launch (list length in device memory).
+void launch_ball_sum(const Tree &t, const float *q, const float *h, const uint32_t *order,
+                     uint32_t m, const float *vt, int nv, int kernel, float *out_sum,
+                     uint32_t *out_count, hipStream_t s);
+void launch_ball_sum_outside_dev(const Tree &t, const float *q, const float *h,
+                                 const uint32_t *list, const uint32_t *nout, const float *vt,
+                                 int nv, int kernel, float *out_sum, uint32_t *out_count,
+                                 hipStream_t s);
+
 // per-row sort of a CSR batch (row offsets `off`, nrows + 1 entries, device):
 // rows of up to csr_sort_row_cap() ids in place; longer rows are appended to
 // long_rows (count in *nlong, zeroed by the caller) for the caller to sort
@@ -434,6 +453,12 @@ nbkd_status query_ball_csr(const Tree &t, const float *q, uint64_t m, float r, u
 nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const float *radii, int nr,
                             uint32_t *out_counts, uint64_t *out_total, uint32_t flags,
                             hipStream_t s);
+
+// h, values: on q's side; nv, kernel and the NULL cases checked by the caller
+// (api.cpp); m > 0
+nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const float *h,
+                           const float *values, int nv, int kernel, float *out_sum,
+                           uint32_t *out_count, uint32_t flags, hipStream_t s);
 
 // fof.hip: friends-of-friends groups of the tree's own points (b finite and
 // >= 0, out_label != nullptr: checked by the caller, api.cpp)

@@ -6,8 +6,8 @@
 // k=1, workers=1)), same properties (n = padded count, size = node count,
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
-// (query_ball_count / query_ball_csr / query_ball_hist) and export() for
-// parity tests.
+// (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
+// (ball_sum), fof_labels and export() for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
 // kdtree/src/cpp/kdtree.cpp:116).  Queries release the GIL, may be called from
@@ -196,6 +196,50 @@ class PyKDTree {
         return py::make_tuple(total, counts);
     }
 
+    // kernel-weighted sums over each query's own ball (nbkd_query_ball_sum):
+    // (raw float32 sums (m, nv), counts uint32 (m,) or None).  values: None
+    // (weight 1, nv = 1) or an (N, nv) array by input row.
+    py::tuple ball_sum(farray points, farray h, std::optional<farray> values, int kernel,
+                       bool count) {
+        check_shape(points);
+        const py::ssize_t m = points.shape(0);
+        if (h.ndim() != 1 || h.shape(0) != m)
+            throw std::runtime_error("h must be a 1D array with one radius per query");
+        py::ssize_t nv = 1;
+        const float *v = nullptr;
+        if (values.has_value()) {
+            if (values->ndim() != 2 || (uint64_t)values->shape(0) != n_in_)
+                throw std::runtime_error("values must be a 2D array of shape (N, nv)");
+            nv = values->shape(1);
+            v = values->data();
+        }
+        if (nv < 1 || nv > NBKD_MAX_VALUES)
+            throw std::runtime_error("the number of value channels must be in [1, " +
+                                     std::to_string(NBKD_MAX_VALUES) + "]");
+        py::array_t<float> sums({m, nv});
+        py::object counts = py::none();
+        uint32_t *c = nullptr;
+        if (count) {
+            py::array_t<uint32_t> arr(m);
+            c = arr.mutable_data();
+            counts = arr;
+        }
+        const float *q = points.data(), *hp = h.data();
+        float *sp = sums.mutable_data();
+        // (m == 0: no arrays to point at; the library returns at once)
+        const float dummy[3] = {0.0f, 0.0f, 0.0f};
+        if (m == 0) q = hp = dummy;
+        nbkd_status st;
+        Interruptible intr;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_query_ball_sum(h_, q, (uint64_t)m, hp, v, (int32_t)nv, (int32_t)kernel, sp,
+                                     c, 0u, nullptr);
+        }
+        intr.finish(st);
+        return py::make_tuple(sums, counts);
+    }
+
     // friends-of-friends groups of the tree's points (nbkd_fof): (labels uint32
     // (N,) = the smallest input row of each point's group, sizes uint32 (N,) =
     // the member count at each label, 0 elsewhere)
@@ -273,6 +317,9 @@ PYBIND11_MODULE(_impl, m) {
              py::arg("per_point") = false)
         .def("query_ball_csr", &PyKDTree::query_ball_csr, py::arg("points"), py::arg("r"),
              py::arg("sorted") = true)
+        .def("ball_sum", &PyKDTree::ball_sum, py::arg("points"), py::arg("h"),
+             py::arg("values") = std::nullopt, py::arg("kernel") = NBKD_KERNEL_CUBIC,
+             py::arg("count") = false)
         .def("fof_labels", &PyKDTree::fof_labels, py::arg("b"))
         .def("export", &PyKDTree::export_tree)
         .def_property_readonly("n", &PyKDTree::num_points)

@@ -1821,6 +1821,101 @@ nbkd_status query_ball_count(const Tree &t, const float *q, uint64_t m, float r,
                          }, s);
 }
 
+// the kernel-weighted sums of m device queries with device radii into device
+// outputs (either may be nullptr); vt = the values in tree order
+static nbkd_status ball_sum_common(const Tree &t, Workspace &ws, const float *q, const float *h,
+                                   uint64_t m, const float *vt, int nv, int kernel,
+                                   float *out_sum, uint32_t *out_count, uint32_t flags,
+                                   hipStream_t s) {
+    if (m == 0) return NBKD_OK;
+    const uint32_t mm = (uint32_t)m;
+    uint32_t *ord = nullptr;
+    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
+                                                : sort_queries(t, ws, q, mm, ord, s);
+    if (rc) return rc;
+    // periodic queries outside [0, L]^3: listed (the length stays in device
+    // memory), every point tested for them
+    uint32_t *list = nullptr;
+    if (t.periodic) {
+        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
+        if (!list) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
+        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(q, mm, t.box, list, list + mm);
+    }
+    TimedScope ts("ball_sum", s);
+    launch_ball_sum(t, q, h, ord, mm, vt, nv, kernel, out_sum, out_count, s);
+    if (list)
+        launch_ball_sum_outside_dev(t, q, h, list, list + mm, vt, nv, kernel, out_sum, out_count,
+                                    s);
+    NBKD_HIP(hipGetLastError());
+    return NBKD_OK;
+}
+
+nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const float *h,
+                           const float *values, int nv, int kernel, float *out_sum,
+                           uint32_t *out_count, uint32_t flags, hipStream_t s) {
+    Workspace &ws = acquire_ws(t);
+    WsCall call(ws, s, std::adopt_lock);
+    NBKD_HIP(call.err);
+    const bool in_dev = (flags & NBKD_INPUT_DEVICE) != 0;
+    // the values once per call: uploaded when they are host memory, then
+    // gathered into tree order (vt[p] = values[row(p)], 1 without values)
+    const float *dvals = values;
+    if (values && !in_dev) {
+        const size_t vb = (size_t)t.n * (size_t)nv * 4;
+        float *up = (float *)ws.get(WS_VALS, vb, s);
+        if (!up) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemcpyAsync(up, values, vb, hipMemcpyHostToDevice, s));
+        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
+        dvals = up;
+    }
+    float *vt = (float *)ws.get(WS_VT, (size_t)t.n8 * (size_t)nv * 4, s);
+    if (!vt) return NBKD_ENOMEM;
+    {
+        TimedScope ts("ball_sum_gather", s);
+        launch_ball_sum_gather(t, dvals, nv, vt, s);
+        NBKD_HIP(hipGetLastError());
+    }
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    if ((flags & dev_io) == dev_io)
+        return ball_sum_common(t, ws, q, h, m, vt, nv, kernel, out_sum, out_count, flags, s);
+    // host arrays stream in batches; each batch's slice of h follows its
+    // queries (the pipeline hands over the batch, not its offset: b0 runs along)
+    size_t ob[2];
+    void *outs[2];
+    int nout = 0;
+    const int isum = out_sum ? nout : -1;
+    if (out_sum) {
+        ob[nout] = (size_t)nv * 4;
+        outs[nout++] = out_sum;
+    }
+    const int icnt = out_count ? nout : -1;
+    if (out_count) {
+        ob[nout] = 4;
+        outs[nout++] = out_count;
+    }
+    uint64_t b0 = 0;
+    const nbkd_status rc = host_pipeline(
+        ws, q, m, flags, nout, ob, outs, 44,
+        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
+            const float *dh = h + b0;
+            if (!in_dev) {
+                float *hb = (float *)ws.get(WS_HRAD, (size_t)nb * 4, st);
+                if (!hb) return NBKD_ENOMEM;
+                NBKD_HIP(hipMemcpyAsync(hb, h + b0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+                dh = hb;
+            }
+            b0 += nb;
+            return ball_sum_common(t, ws, dq, dh, nb, vt, nv, kernel,
+                                   isum >= 0 ? (float *)o[isum] : nullptr,
+                                   icnt >= 0 ? (uint32_t *)o[icnt] : nullptr, flags | dev_io, st);
+        }, s);
+    if (rc) return rc;
+    // the caller's h (pageable memory) has been read when the call returns
+    if (!in_dev) NBKD_HIP(hipStreamSynchronize(s));
+    return NBKD_OK;
+}
+
 // the radius histogram of m device queries: rows into the device array
 // out_counts (or nullptr), column sums added to the device counters tot (or
 // nullptr)

@@ -11,7 +11,9 @@ Additions (no reference counterpart): ``query_ball`` (scipy-style radius
 query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
 many radii in one tree walk), ``fof`` / ``fof_labels`` (friends-of-friends
 groups of the tree's points), ``density`` (local number density from the k-th
-neighbour distance or from a radius count), a ``device`` keyword, and
+neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
+``interpolate`` (kernel-weighted sums over each query's own ball: the gather
+form of SPH), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
 no pickle inside) and pickling.  A restored tree is rebuilt on the GPU from
 the saved points (the build is deterministic: same node table; ~55 ms at 1e8),
@@ -37,6 +39,12 @@ except ImportError as e:  # fail loudly: no CPU path exists
         f"(hipcc for gfx950 + pybind11). Original error: {e}") from e
 
 __all__ = ["KDTree", "cKDTree", "device_count"]
+
+# kernel name -> (NBKD_KERNEL_* code, 3-D normalisation sigma of K(d / h) / h^3
+# with support radius h)
+_KERNELS = {"tophat": (0, 3.0 / (4.0 * math.pi)), "cubic": (1, 8.0 / math.pi),
+            "wendland": (2, 21.0 / (2.0 * math.pi))}
+_MAX_VALUES = 4  # NBKD_MAX_VALUES
 
 
 def _flatten(points):
@@ -209,6 +217,114 @@ class KDTree(cKDTree):
             return k / (4.0 / 3.0 * math.pi * rk ** 3)
         c = self.query_ball(points, r, return_length=True).astype(np.float64)
         return c / (4.0 / 3.0 * math.pi * float(r) ** 3)
+
+    # ---------------------------------------------------------------- kernel sums
+    def _sum_args(self, points, h, values, kernel):
+        """Checked arguments of a kernel sum: (flat float32 points, output
+        shape, float32 radii (M,), float32 values (N, nv) or None, whether
+        values was 1-D or absent, kernel code).  Runs before any device call."""
+        if kernel not in _KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(_KERNELS)}")
+        points, shape = _flatten(points)
+        m = np.asarray(points).shape[0]
+        out_shape = tuple(shape[:-1]) if shape is not None else (m,)
+        hh = np.asarray(h, dtype=np.float64)
+        if not np.all(np.isfinite(hh)) or np.any(hh < 0):
+            raise ValueError("every radius h must be finite and >= 0")
+        try:
+            hh = np.broadcast_to(hh, out_shape).reshape(-1)
+        except ValueError:
+            raise ValueError(f"h of shape {np.shape(h)} does not broadcast to the queries "
+                             f"{out_shape}") from None
+        vals, flat = None, True
+        if values is not None:
+            vals = np.asarray(values, dtype=np.float32)
+            if vals.ndim not in (1, 2) or vals.shape[0] != self._n_input:
+                raise ValueError(f"values must be (N,) or (N, nv) with N = {self._n_input} "
+                                 f"the tree's point count, got {vals.shape}")
+            flat = vals.ndim == 1
+            if not flat and not 1 <= vals.shape[1] <= _MAX_VALUES:
+                raise ValueError(f"values holds {vals.shape[1]} channels: 1 to {_MAX_VALUES} "
+                                 "per call")
+            vals = np.ascontiguousarray(vals.reshape(self._n_input, -1))
+        return (points, out_shape, np.ascontiguousarray(hh, dtype=np.float32), vals, flat,
+                _KERNELS[kernel][0])
+
+    def kernel_sum(self, points: np.ndarray, h, values=None, kernel: str = "cubic",
+                   return_count: bool = False):
+        """Kernel-weighted sums over each query's own ball, summed on the GPU:
+        ``sum_j values[j] * K(d_ij / h_i)`` over the tree points with
+        d2 <= h_i*h_i in float32 (the ``query_ball`` predicate at r = h_i).
+
+        h : a scalar or an array broadcast to the queries, finite and >= 0.
+        values : None (weight 1), (N,) or (N, nv <= 4), indexed like the
+            tree's input points.
+        kernel : "tophat" (K = 1), "cubic" (the M4 spline
+            1 - 6u^2 + 6u^3 | 2(1 - u)^3) or "wendland" ((1 - u)^4 (1 + 4u)).
+
+        Returns the raw (un-normalised) sums as float64, shape
+        points.shape[:-1] (+ (nv,) for 2-D values); with return_count=True
+        also the uint32 neighbour counts.  The device sums in float32, one
+        accumulator per (query, channel) in a fixed order: identical calls
+        give identical arrays.
+        """
+        points, out_shape, hh, vals, flat, code = self._sum_args(points, h, values, kernel)
+        sums, counts = super().ball_sum(points, hh, vals, code, bool(return_count))
+        sums = sums.astype(np.float64).reshape(out_shape if flat else out_shape + (sums.shape[1],))
+        if return_count:
+            return sums, counts.reshape(out_shape)
+        return sums
+
+    def sph_density(self, points: Optional[np.ndarray] = None, k: int = 32, mass=None,
+                    kernel: str = "cubic", h=None):
+        """SPH (gather) density ``sigma / h_i^3 * sum_j m_j K(d_ij / h_i)``
+        with sigma = 3/(4 pi), 8/pi, 21/(2 pi) for "tophat", "cubic" and
+        "wendland".  points=None: at the tree's own points.  h: the smoothing
+        lengths, or None for the k-th neighbour distance.  mass: (N,) or None
+        (unit masses: a number density).  float64; inf or NaN where h is 0."""
+        if kernel not in _KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(_KERNELS)}")
+        if mass is not None and (np.ndim(mass) != 1 or np.shape(mass)[0] != self._n_input):
+            raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point count")
+        if h is not None:
+            hh = np.asarray(h, dtype=np.float64)
+            if not np.all(np.isfinite(hh)) or np.any(hh < 0):
+                raise ValueError("every radius h must be finite and >= 0")
+        if points is None:
+            points = self.points()
+        if h is None:
+            h = self.kth_distance(points, int(k))
+        s = self.kernel_sum(points, h, mass, kernel)
+        h64 = np.broadcast_to(np.asarray(h, dtype=np.float32).astype(np.float64), s.shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return _KERNELS[kernel][1] * s / h64 ** 3
+
+    def interpolate(self, points: np.ndarray, h, field, mass=None, kernel: str = "cubic"):
+        """SPH interpolation of a per-particle field at arbitrary points:
+        ``sum_j m_j A_j K / sum_j m_j K`` over each query's ball of radius
+        h_i, in one device call (channels m*A_1..m*A_c, m).  field: (N,) or
+        (N, c <= 3); mass: (N,) or None (unit masses).  float64, shape
+        points.shape[:-1] (+ (c,)); NaN where the ball is empty."""
+        if kernel not in _KERNELS:
+            raise ValueError(f"unknown kernel {kernel!r}: one of {sorted(_KERNELS)}")
+        f = np.asarray(field, dtype=np.float64)
+        if f.ndim not in (1, 2) or f.shape[0] != self._n_input:
+            raise ValueError(f"field must be (N,) or (N, c) with N = {self._n_input} the tree's "
+                             f"point count, got {f.shape}")
+        if f.ndim == 2 and not 1 <= f.shape[1] <= _MAX_VALUES - 1:
+            raise ValueError(f"field holds {f.shape[1]} channels: 1 to {_MAX_VALUES - 1} per call")
+        if mass is None:
+            w = np.ones(self._n_input, np.float64)
+        else:
+            w = np.asarray(mass, dtype=np.float64)
+            if w.ndim != 1 or w.shape[0] != self._n_input:
+                raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point "
+                                 "count")
+        vals = np.concatenate([f.reshape(self._n_input, -1) * w[:, None], w[:, None]], axis=1)
+        s = self.kernel_sum(points, h, vals.astype(np.float32), kernel)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = s[..., :-1] / s[..., -1:]
+        return out[..., 0] if f.ndim == 1 else out
 
     # ---------------------------------------------------------------- persistence
     def points(self) -> np.ndarray:
