@@ -244,6 +244,81 @@ nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t 
                                 uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): the group catalogue of a labelling of the
+ * tree's points, the halo finder's second step: which rows are in each group,
+ * and the float64 moments from which mass, centre, extent, bulk velocity and
+ * velocity dispersion follow.
+ *   label       (n,) uint32 by input row (the build's permutation, also after
+ *               nbkd_set_ids), canonical: label[i] < n and
+ *               label[label[i]] == label[i].  The output of nbkd_fof is; any
+ *               canonical labelling is accepted.  A device kernel counts the
+ *               violations: a nonzero count is NBKD_EINVAL with a message, and
+ *               nothing is written but the two counts, which are zeroed.
+ *   weight      (n,) float32, or NULL: weight 1
+ *   values      (n, nv) row-major float32, or NULL with nv == 0;
+ *               0 <= nv <= NBKD_MAX_VALUES
+ *               label, weight and values are on one side: host, or device with
+ *               NBKD_INPUT_DEVICE
+ *   min_members a group is kept when it has at least this many members (0 is
+ *               treated as 1).  Kept groups are numbered g = 0..G-1 by ascending
+ *               label (the group's "head": its smallest row).
+ *   out_ngroups, out_nmembers   host memory, required: G, and K = the number of
+ *               rows in kept groups.  They are always written.
+ *   group_capacity, member_capacity   if G > group_capacity or
+ *               K > member_capacity no other output is written and the status
+ *               is NBKD_OK: a sizing call is a call with both capacities 0, as
+ *               with nbkd_query_ball_csr.
+ * The other outputs are host memory, or device memory with NBKD_OUTPUT_DEVICE;
+ * each may be NULL:
+ *   out_head    (G,) uint32   the head of group g
+ *   out_size    (G,) uint32   its member count
+ *   out_offsets (G+1,) uint64 and
+ *   out_members (K,) uint32   out_members[out_offsets[g] : out_offsets[g+1]] =
+ *               the input rows of group g, ascending
+ *   out_dmax    (G,) float32  the maximum over members and axes of |d| (exact:
+ *               a maximum does not depend on the order).  On a periodic tree
+ *               dmax >= L/2 means the group spans the box and the unwrapping
+ *               relative to the head is not trustworthy.
+ *   out_moments (G, NBKD_GROUP_MOMENTS(nv)) row-major float64; row g holds, over
+ *               the members j of g,
+ *                 [sum w, sum w*dx, sum w*dy, sum w*dz,
+ *                  sum w*((dx*dx + dy*dy) + dz*dz),
+ *                  sum w*v_c (c < nv), sum w*(v_c*v_c) (c < nv)]
+ * d is the float32 offset of member j from the head's position: per axis
+ * d = fl(p_j - p_head), and on a periodic tree the one of d, fl(d - L),
+ * fl(d + L) with the smallest magnitude (ties to the earlier in that order).
+ * Each term is formed in float64 from the float32 inputs exactly as written,
+ * without fused multiply-adds (w*d is exact: 24 x 24 bits).
+ * Deterministic: there are no floating-point atomics, and the summation order
+ * is a fixed function of the sorted member list (64 consecutive members per
+ * wave, a log-step segmented scan over the lanes, then a fixed-shape sum of
+ * the per-wave partials of each group that crosses a wave).  It does not
+ * depend on the tree, its leaf size, the launch geometry or timing: two calls
+ * with the same labels, weights and values give moments equal under ==, also
+ * across trees built from the same points with different leaf_size.
+ * Any order of summing m float64 terms t_i errs by at most
+ * (m - 1) * 2^-53 * sum |t_i|.
+ * NBKD_EINVAL before any device call, outputs untouched: NULL tree, label,
+ * out_ngroups or out_nmembers; nv out of range; values == NULL with nv != 0;
+ * values != NULL with nv == 0.  n == 0 is NBKD_OK with both counts 0.  Padding
+ * points are in no group.  The call always waits (the counts are host memory).
+ * Scratch: 12 bytes per point (counts and two scans; one of them later holds
+ * row -> tree position), 16 bytes per kept row (the radix sort's two key /
+ * row pairs), 2 * NBKD_GROUP_MOMENTS(nv) * 8 + 12 bytes per 64 kept rows (the
+ * per-wave partials), the uploaded host inputs and the staged host outputs.
+ */
+#define NBKD_GROUP_MOMENTS(nv) (5 + 2 * (nv))
+nbkd_status nbkd_group_catalog(const nbkd_tree *tree, const uint32_t *label,
+                               const float *weight, const float *values, int32_t nv,
+                               uint32_t min_members,
+                               uint64_t group_capacity, uint64_t member_capacity,
+                               uint64_t *out_ngroups, uint64_t *out_nmembers,
+                               uint32_t *out_head, uint32_t *out_size,
+                               uint64_t *out_offsets, uint32_t *out_members,
+                               double *out_moments, float *out_dmax,
+                               uint32_t flags, void *stream);
+
+/*
  * NEW: neighbour lists within r in CSR form.  out_offsets is (m+1,) uint64
  * (always host memory); out_idx receives offsets[m] original point indices,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row

@@ -54,6 +54,9 @@ _PROTOS = {
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
     "nbkd_fof": (_i32, [_c_p, ctypes.c_float, _c_p, _c_p, ctypes.POINTER(_u64), _u32, _c_p]),
+    "nbkd_group_catalog": (_i32, [_c_p, _c_p, _c_p, _c_p, _i32, _u32, _u64, _u64,
+                                  ctypes.POINTER(_u64), ctypes.POINTER(_u64), _c_p, _c_p, _c_p,
+                                  _c_p, _c_p, _c_p, _u32, _c_p]),
     "nbkd_tree_info": (_i32, [_c_p, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                               ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_float),
                               ctypes.POINTER(_i32)]),
@@ -306,6 +309,65 @@ class Tree:
         """nbkd_fof into device arrays ((n,) uint32 each); returns once enqueued."""
         _check(lib().nbkd_fof(self.h, float(b), labels_ptr, sizes_ptr, None,
                               NBKD_OUTPUT_DEVICE, stream))
+
+    def group_catalog(self, labels, min_members=1, weight=None, values=None, members=True):
+        """nbkd_group_catalog of host arrays, sized with one call and filled
+        with a second: (head (G,) uint32, size (G,) uint32, offsets (G + 1,)
+        uint64 or None, members (K,) uint32 or None, moments (G, 5 + 2 nv)
+        float64, dmax (G,) float32).  labels: (n,) canonical (the output of
+        fof); weight: (n,) or None; values: (n,) or (n, nv) or None."""
+        n = self.npoints
+        lab = np.ascontiguousarray(labels, dtype=np.uint32)
+        if lab.shape != (n,):
+            raise ValueError("labels must be (n,) with n the tree's point count")
+        w = None
+        if weight is not None:
+            w = _host_f32(weight)
+            if w.shape != (n,):
+                raise ValueError("weight must be (n,) with n the tree's point count")
+        v, nv = None, 0
+        if values is not None:
+            v = _host_f32(values)
+            if v.ndim not in (1, 2) or v.shape[0] != n:
+                raise ValueError("values must be (n,) or (n, nv) with n the tree's point count")
+            v = np.ascontiguousarray(v.reshape(n, -1))
+            nv = v.shape[1]
+        wp = None if w is None else w.ctypes.data
+        vp = None if v is None else v.ctypes.data
+        ng, nm = _u64(), _u64()
+        _check(lib().nbkd_group_catalog(self.h, lab.ctypes.data, wp, vp, nv, int(min_members), 0,
+                                        0, ctypes.byref(ng), ctypes.byref(nm), None, None, None,
+                                        None, None, None, 0, None))
+        G, K = ng.value, nm.value
+        head, size = np.empty(G, np.uint32), np.empty(G, np.uint32)
+        off = np.zeros(G + 1, np.uint64) if members else None
+        mem = np.empty(K, np.uint32) if members else None
+        mom = np.empty((G, 5 + 2 * nv), np.float64)
+        dmax = np.empty(G, np.float32)
+        if G:
+            _check(lib().nbkd_group_catalog(self.h, lab.ctypes.data, wp, vp, nv,
+                                            int(min_members), G, K, ctypes.byref(ng),
+                                            ctypes.byref(nm), head.ctypes.data, size.ctypes.data,
+                                            off.ctypes.data if members else None,
+                                            mem.ctypes.data if members else None,
+                                            mom.ctypes.data, dmax.ctypes.data, 0, None))
+        return head, size, off, mem, mom, dmax
+
+    def group_catalog_device(self, labels_ptr, weight_ptr, values_ptr, nv, min_members,
+                             group_capacity, member_capacity, head_ptr=None, size_ptr=None,
+                             offsets_ptr=None, members_ptr=None, moments_ptr=None, dmax_ptr=None,
+                             stream=None):
+        """nbkd_group_catalog with device inputs and device outputs (raw
+        pointers, any output may be None); returns (G, K).  Nothing but the
+        counts is written when G > group_capacity or K > member_capacity."""
+        ng, nm = _u64(), _u64()
+        _check(lib().nbkd_group_catalog(self.h, labels_ptr, weight_ptr, values_ptr, int(nv),
+                                        int(min_members), int(group_capacity),
+                                        int(member_capacity), ctypes.byref(ng), ctypes.byref(nm),
+                                        head_ptr, size_ptr, offsets_ptr, members_ptr,
+                                        moments_ptr, dmax_ptr,
+                                        NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+        return ng.value, nm.value
 
     def ball_csr(self, q, r, sorted=False):
         """CSR radius query of host queries: (offsets (m + 1,) uint64, ids);

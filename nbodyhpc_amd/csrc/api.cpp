@@ -696,6 +696,46 @@ nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_group_catalog(const nbkd_tree *tree, const uint32_t *label,
+                               const float *weight, const float *values, int32_t nv,
+                               uint32_t min_members, uint64_t group_capacity,
+                               uint64_t member_capacity, uint64_t *out_ngroups,
+                               uint64_t *out_nmembers, uint32_t *out_head, uint32_t *out_size,
+                               uint64_t *out_offsets, uint32_t *out_members,
+                               double *out_moments, float *out_dmax, uint32_t flags,
+                               void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !label || !out_ngroups || !out_nmembers) {
+        set_error("nbkd_group_catalog: NULL argument (tree, label, out_ngroups or out_nmembers)");
+        return NBKD_EINVAL;
+    }
+    if (nv < 0 || nv > NBKD_MAX_VALUES) {
+        set_error("nbkd_group_catalog: the number of value channels must be in [0, " +
+                  std::to_string(NBKD_MAX_VALUES) + "], got " + std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    if (!values && nv != 0) {
+        set_error("nbkd_group_catalog: values == NULL needs nv == 0, got " + std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    if (values && nv == 0) {
+        set_error("nbkd_group_catalog: values given with nv == 0");
+        return NBKD_EINVAL;
+    }
+    if (tree->t.n == 0) { // no rows, no groups: no device call
+        *out_ngroups = 0;
+        *out_nmembers = 0;
+        return NBKD_OK;
+    }
+    DeviceGuard g(tree->t.device);
+    return group_catalog(tree->t, label, weight, values, nv, min_members, group_capacity,
+                         member_capacity, out_ngroups, out_nmembers, out_head, out_size,
+                         out_offsets, out_members, out_moments, out_dmax, flags,
+                         (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_query_ball_csr(const nbkd_tree *tree, const float *q, uint64_t m, float r,
                                 uint64_t *out_offsets, uint32_t *out_idx, uint64_t capacity,
                                 uint32_t flags, void *stream) {

@@ -470,6 +470,19 @@ nbkd_status fof(const Tree &t, float b, uint32_t *out_label, uint32_t *out_size,
 nbkd_status sort_pairs(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
                        uint32_t n, int nbits, hipStream_t s, uint32_t **vout);
 
+// query.hip: exclusive scan of a uint32 array in place (3 launches)
+nbkd_status excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s);
+
+// group.hip: the kept groups of a canonical labelling, their member lists and
+// float64 moments (the NULL cases, nv and the counts' pointers checked by the
+// caller, api.cpp)
+nbkd_status group_catalog(const Tree &t, const uint32_t *label, const float *weight,
+                          const float *values, int nv, uint32_t min_members,
+                          uint64_t group_capacity, uint64_t member_capacity,
+                          uint64_t *out_ngroups, uint64_t *out_nmembers, uint32_t *out_head,
+                          uint32_t *out_size, uint64_t *out_offsets, uint32_t *out_members,
+                          double *out_moments, float *out_dmax, uint32_t flags, hipStream_t s);
+
 // deposit.hip: spheres onto a voxel grid (render_points_volume / render_points)
 nbkd_status deposit(const float *xyz, const float *weight, const float *radius, uint64_t n, int gx,
                     int gy, int nz, float ppu, const float *period, int S, int mode, int x0, int wx,

@@ -7,7 +7,7 @@
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
 // (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
-// (ball_sum), fof_labels and export() for parity tests.
+// (ball_sum), fof_labels, group_moments and export() for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
 // kdtree/src/cpp/kdtree.cpp:116).  Queries release the GIL, may be called from
@@ -255,6 +255,70 @@ class PyKDTree {
         return {labels, sizes};
     }
 
+    // the group catalogue of a canonical labelling (nbkd_group_catalog), sized
+    // with one call and filled with a second: (head uint32 (G,), size uint32
+    // (G,), offsets uint64 (G + 1,) or None, members uint32 (K,) or None,
+    // moments float64 (G, 5 + 2 nv), dmax float32 (G,))
+    py::tuple group_moments(py::array_t<uint32_t, py::array::c_style | py::array::forcecast> labels,
+                            uint32_t min_members, std::optional<farray> weight,
+                            std::optional<farray> values, bool members) {
+        if (labels.ndim() != 1 || (uint64_t)labels.shape(0) != n_in_)
+            throw std::runtime_error("labels must be a 1D array with one label per point");
+        const float *w = nullptr, *v = nullptr;
+        py::ssize_t nv = 0;
+        if (weight.has_value()) {
+            if (weight->ndim() != 1 || (uint64_t)weight->shape(0) != n_in_)
+                throw std::runtime_error("weight must be a 1D array with one weight per point");
+            w = weight->data();
+        }
+        if (values.has_value()) {
+            if (values->ndim() != 2 || (uint64_t)values->shape(0) != n_in_)
+                throw std::runtime_error("values must be a 2D array of shape (N, nv)");
+            nv = values->shape(1);
+            if (nv < 1 || nv > NBKD_MAX_VALUES)
+                throw std::runtime_error("the number of value channels must be in [1, " +
+                                         std::to_string(NBKD_MAX_VALUES) + "]");
+            v = values->data();
+        }
+        const uint32_t *l = labels.data();
+        uint64_t G = 0, K = 0;
+        nbkd_status st;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_group_catalog(h_, l, w, v, (int32_t)nv, min_members, 0, 0, &G, &K, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr);
+        }
+        check(st);
+        py::array_t<uint32_t> head((py::ssize_t)G), size((py::ssize_t)G);
+        py::array_t<double> mom({(py::ssize_t)G, (py::ssize_t)NBKD_GROUP_MOMENTS(nv)});
+        py::array_t<float> dmax((py::ssize_t)G);
+        py::object offsets = py::none(), mem = py::none();
+        uint64_t *op = nullptr;
+        uint32_t *mp = nullptr;
+        if (members) {
+            py::array_t<uint64_t> o((py::ssize_t)G + 1);
+            py::array_t<uint32_t> m((py::ssize_t)K);
+            op = o.mutable_data();
+            mp = m.mutable_data();
+            op[0] = 0; // (G == 0: the library writes nothing)
+            offsets = o;
+            mem = m;
+        }
+        if (G > 0) {
+            uint32_t *hp = head.mutable_data(), *sp = size.mutable_data();
+            double *dp = mom.mutable_data();
+            float *xp = dmax.mutable_data();
+            uint64_t G2 = 0, K2 = 0;
+            {
+                py::gil_scoped_release nogil;
+                st = nbkd_group_catalog(h_, l, w, v, (int32_t)nv, min_members, G, K, &G2, &K2, hp,
+                                        sp, op, mp, dp, xp, 0u, nullptr);
+            }
+            check(st);
+        }
+        return py::make_tuple(head, size, offsets, mem, mom, dmax);
+    }
+
     // rows sorted ascending on the device unless sorted=false (NBKD_SORTED);
     // both passes stream in batches and poll Ctrl-C between them
     std::pair<py::array_t<uint64_t>, py::array_t<uint32_t>> query_ball_csr(farray points, float r,
@@ -321,6 +385,9 @@ PYBIND11_MODULE(_impl, m) {
              py::arg("values") = std::nullopt, py::arg("kernel") = NBKD_KERNEL_CUBIC,
              py::arg("count") = false)
         .def("fof_labels", &PyKDTree::fof_labels, py::arg("b"))
+        .def("group_moments", &PyKDTree::group_moments, py::arg("labels"),
+             py::arg("min_members") = 1, py::arg("weight") = std::nullopt,
+             py::arg("values") = std::nullopt, py::arg("members") = true)
         .def("export", &PyKDTree::export_tree)
         .def_property_readonly("n", &PyKDTree::num_points)
         .def_property_readonly("size", &PyKDTree::num_nodes)

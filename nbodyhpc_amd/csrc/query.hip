@@ -1220,6 +1220,11 @@ nbkd_status sort_pairs(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, 
     return radix_sort(ws, k0, v0, k1, v1, n, nbits, s, vout);
 }
 
+// the exclusive scan for other translation units (group.hip)
+nbkd_status excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s) {
+    return device_excl_scan(ws, a, n, s);
+}
+
 namespace {
 
 bool collect_disabled() {

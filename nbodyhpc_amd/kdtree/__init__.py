@@ -10,7 +10,8 @@ extension or without a GPU the constructor raises.
 Additions (no reference counterpart): ``query_ball`` (scipy-style radius
 query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
 many radii in one tree walk), ``fof`` / ``fof_labels`` (friends-of-friends
-groups of the tree's points), ``density`` (local number density from the k-th
+groups of the tree's points), ``fof_catalog`` (members, mass, centre, extent
+and value moments per group, reduced on the GPU), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
 ``interpolate`` (kernel-weighted sums over each query's own ball: the gather
 form of SPH), a ``device`` keyword, and
@@ -195,6 +196,85 @@ class KDTree(cKDTree):
         if return_sizes:
             return group, sizes[heads].astype(np.int64)
         return group
+
+    def fof_catalog(self, linking_length: Optional[float], min_members: int = 20, mass=None,
+                    values=None, members: bool = False, labels=None):
+        """The group catalogue of the friends-of-friends groups (or of any
+        canonical labelling given as ``labels``: labels[i] = the smallest
+        input row of i's group; ``linking_length`` may then be None), reduced
+        on the GPU in float64 with a fixed summation order.
+
+        mass : (N,) weights or None (unit masses).
+        values : (N,) or (N, nv <= 4) per-particle channels (velocities, ...).
+
+        Groups with at least ``min_members`` members are numbered exactly as
+        ``fof(linking_length, min_members)`` numbers them: descending size,
+        ties by the smaller head.  Returns a dict of arrays over the groups:
+        ``head`` (smallest member row), ``size``, ``mass`` (sum of weights),
+        ``center`` float64 (G, 3) (wrapped into [0, L) on a periodic tree;
+        offsets are unwrapped relative to the head), ``rms_radius``, ``mean``
+        and ``dispersion`` (G, nv) of the value channels, ``spans_box`` (bool:
+        a member lies L/2 or more from the head along an axis, so the
+        unwrapped centre is not trustworthy; all False on a non-periodic
+        tree), and with members=True ``offsets`` (G + 1,) and ``members``:
+        members[offsets[g]:offsets[g + 1]] = the rows of group g, ascending.
+        """
+        n = self._n_input
+        if labels is None and linking_length is None:
+            raise ValueError("give labels or a linking_length")
+        w = None
+        if mass is not None:
+            w = np.asarray(mass, dtype=np.float32)
+            if w.shape != (n,):
+                raise ValueError(f"mass must be (N,) with N = {n} the tree's point count")
+        v, nv = None, 0
+        if values is not None:
+            v = np.asarray(values, dtype=np.float32)
+            if v.ndim not in (1, 2) or v.shape[0] != n:
+                raise ValueError(f"values must be (N,) or (N, nv) with N = {n} the tree's point "
+                                 f"count, got {v.shape}")
+            v = np.ascontiguousarray(v.reshape(n, -1))
+            nv = v.shape[1]
+            if not 1 <= nv <= _MAX_VALUES:
+                raise ValueError(f"values holds {nv} channels: 1 to {_MAX_VALUES} per call")
+        if labels is not None:
+            lab = np.asarray(labels)
+            if lab.shape != (n,):
+                raise ValueError(f"labels must be (N,) with N = {n} the tree's point count")
+            lab = np.ascontiguousarray(lab, dtype=np.uint32)
+        else:
+            lab, _ = super().fof_labels(float(linking_length))
+        head, size, off, mem, mom, dmax = super().group_moments(
+            lab, max(int(min_members), 1), w, v, bool(members))
+        # fof()'s numbering: descending size, ties by the smaller head (the
+        # device's order is ascending heads, the sort is stable)
+        order = np.argsort(-size.astype(np.int64), kind="stable")
+        head, size, mom, dmax = head[order], size[order], mom[order], dmax[order]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m0 = mom[:, 0]
+            dbar = mom[:, 1:4] / m0[:, None]
+            center = self.points()[head].astype(np.float64) + dbar
+            rms = np.sqrt(np.maximum(mom[:, 4] / m0 - np.sum(dbar * dbar, axis=1), 0.0))
+            mean = mom[:, 5:5 + nv] / m0[:, None]
+            disp = np.sqrt(np.maximum(mom[:, 5 + nv:5 + 2 * nv] / m0[:, None] - mean * mean, 0.0))
+        if self.periodic:
+            L = float(self.boxsize)
+            center = center % L
+            center[center >= L] = 0.0  # (a tiny negative wraps to L in float64)
+            spans = dmax >= np.float32(0.5) * np.float32(self.boxsize)
+        else:
+            spans = np.zeros(head.shape[0], bool)
+        cat = {"head": head, "size": size, "mass": m0.copy(), "center": center,
+               "rms_radius": rms, "mean": mean, "dispersion": disp, "spans_box": spans}
+        if members:
+            cnt = np.diff(off.astype(np.int64))[order]
+            new_off = np.zeros(head.shape[0] + 1, np.int64)
+            np.cumsum(cnt, out=new_off[1:])
+            # gather each group's rows into its new place
+            src = np.repeat(off[:-1].astype(np.int64)[order] - new_off[:-1], cnt)
+            cat["offsets"] = new_off.astype(np.uint64)
+            cat["members"] = mem[src + np.arange(mem.shape[0], dtype=np.int64)]
+        return cat
 
     def kth_distance(self, points: np.ndarray, k: int):
         """Distance to the k-th nearest neighbour of each point: column k-1 of
