@@ -244,6 +244,70 @@ nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t 
                                 uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): Barnes-Hut potentials and accelerations at
+ * m query points from the tree's points as masses, G = 1 (the caller scales),
+ * Plummer softening eps: what unbinding, the most-bound particle and a force
+ * check of a snapshot need.
+ *   q        (m, 3) float32
+ *   mass     (n,) float32 on the same side as q, indexed by input row (the
+ *            build's permutation, also after nbkd_set_ids), or NULL: mass 1.
+ *            Masses must be finite and >= 0; otherwise the values are
+ *            unspecified, but nothing faults.
+ *   theta    the opening angle, 0 <= theta < 1; 0 is the direct sum
+ *   eps      the softening length, finite and >= 0
+ *   out_phi  (m,) float32 or NULL;  out_acc (m, 3) row-major float32 or NULL; at
+ *            least one; both host, or both device with NBKD_OUTPUT_DEVICE
+ * Non-periodic trees only: a periodic tree is NBKD_EINVAL (Ewald sums are not
+ * provided).
+ * Everything below is float32 without fused multiply-adds unless float64 is
+ * stated.
+ * Node moments.  Each node with at least one real point has moments; padding
+ * points are in no node's moments (no node is without a real point).
+ *   M64 = sum m_j and S64 = sum m_j*p_j per axis, in float64, each product
+ *   formed in float64 (exact: 24 x 24 bits); in a leaf by ascending tree
+ *   position into one accumulator, in an internal node the left child's sums
+ *   plus the right child's.  M = (float)M64; c = (float)(S64 / M64) per axis,
+ *   the division in float64; if M64 == 0, c = 0.5f*(lo + hi) of the tight box.
+ *   The tight box [lo, hi] is the exact min / max over the node's real points;
+ *   e = hi - lo per axis; s2 = (e.x*e.x + e.y*e.y) + e.z*e.z.
+ * Opening test, per query, at every node (leaves too): d = c - q per axis,
+ * d2 = (d.x*d.x + d.y*d.y) + d.z*d.z; the node is accepted iff
+ * theta*theta > 0 and s2 <= (theta*theta)*d2.  c lies inside the tight box and
+ * theta < 1, so a query is never inside an accepted node's box.
+ * Terms.  The walk starts at the root.  An accepted node adds the monopole
+ * (M, c).  A leaf that is not accepted adds each of its real points (m_j, p_j)
+ * with d = p_j - q, by ascending tree position.  An internal node that is not
+ * accepted visits its left child, then its right child.
+ * One term with mass mu at offset d (d2 as above): d2 == 0 adds nothing (a self
+ * query, any coincident point, for every eps); otherwise
+ *   r2 = d2 + eps*eps;  inv = 1.0f / sqrtf(r2);
+ *   phi -= mu*inv;  w = mu*((inv*inv)*inv);
+ *   acc.x += w*d.x;  acc.y += w*d.y;  acc.z += w*d.z.
+ * phi and acc start at 0.
+ * Deterministic: each query is summed by one lane into one float32 register per
+ * component, in exactly this order.  The order depends on the tree, the query,
+ * theta and eps only: not on the other queries of the call, the path (the
+ * tree's build array as device queries takes the self-order path, other
+ * queries are bucketed and sorted), the host batch size, the grid or timing.
+ * There are no floating-point atomics.  Two calls give arrays equal under ==,
+ * and so do the self-order path, the bucketed path and every host batch size.
+ * A call with one output gives that output exactly as the call with both.
+ * NBKD_EINVAL before any device call, outputs untouched: NULL tree or q; both
+ * outputs NULL; theta NaN, negative or >= 1; eps NaN, negative or infinite;
+ * m >= 2^32; a periodic tree.  m == 0 is NBKD_OK.  With device inputs and
+ * outputs the call returns once the work is enqueued, as nbkd_query_ball_sum
+ * does.  Host arrays stream in batches (see above); mass is uploaded once per
+ * call.  Scratch: 4 bytes per point (the masses in tree order) and 100 bytes
+ * per node (a 32-byte record M, c, s2 per node, the float64 sums, the tight
+ * box, a done word) of the call's workspace; the moments are rebuilt per call
+ * (one launch over the leaves, one per tree level above them).
+ */
+nbkd_status nbkd_gravity(const nbkd_tree *tree, const float *q, uint64_t m,
+                         const float *mass, float theta, float eps,
+                         float *out_phi, float *out_acc,
+                         uint32_t flags, void *stream);
+
+/*
  * NEW (no reference counterpart): the group catalogue of a labelling of the
  * tree's points, the halo finder's second step: which rows are in each group,
  * and the float64 moments from which mass, centre, extent, bulk velocity and

@@ -51,6 +51,8 @@ _PROTOS = {
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_ball_sum": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _u32,
                                    _c_p]),
+    "nbkd_gravity": (_i32, [_c_p, _c_p, _u64, _c_p, ctypes.c_float, ctypes.c_float, _c_p, _c_p,
+                            _u32, _c_p]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
     "nbkd_fof": (_i32, [_c_p, ctypes.c_float, _c_p, _c_p, ctypes.POINTER(_u64), _u32, _c_p]),
@@ -293,6 +295,32 @@ class Tree:
         _check(lib().nbkd_query_ball_sum(self.h, q_ptr, int(m), h_ptr, values_ptr, int(nv),
                                          int(kernel), sum_ptr, count_ptr,
                                          NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+
+    def gravity(self, q, mass=None, theta=0.5, eps=0.0, phi=True, acc=True):
+        """nbkd_gravity of host arrays, G = 1: (phi (m,) float32 or None, acc
+        (m, 3) float32 or None).  mass: (n,) by input row, or None (mass 1);
+        theta: the opening angle in [0, 1), 0 = the direct sum; eps: the
+        Plummer softening."""
+        q = _host_f32(q).reshape(-1, 3)
+        m = q.shape[0]
+        w = None
+        if mass is not None:
+            w = _host_f32(mass)
+            if w.shape != (self.npoints,):
+                raise ValueError("mass must be (n,) with n the tree's point count")
+        p = np.empty(m, np.float32) if phi else None
+        a = np.empty((m, 3), np.float32) if acc else None
+        _check(lib().nbkd_gravity(self.h, q.ctypes.data, m, None if w is None else w.ctypes.data,
+                                  float(theta), float(eps), p.ctypes.data if phi else None,
+                                  a.ctypes.data if acc else None, 0, None))
+        return p, a
+
+    def gravity_device(self, q_ptr, m, mass_ptr, theta, eps, phi_ptr, acc_ptr=None, stream=None):
+        """Device queries, masses ((n,) or None) and outputs ((m,) float32
+        potentials and / or (m, 3) float32 accelerations); returns once enqueued."""
+        _check(lib().nbkd_gravity(self.h, q_ptr, int(m), mass_ptr, float(theta), float(eps),
+                                  phi_ptr, acc_ptr, NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE,
+                                  stream))
 
     def fof(self, b, sizes=True):
         """nbkd_fof into host arrays: (labels (n,) uint32 = the smallest input

@@ -679,6 +679,42 @@ nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t 
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_gravity(const nbkd_tree *tree, const float *q, uint64_t m, const float *mass,
+                         float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
+                         void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q) {
+        set_error("nbkd_gravity: NULL argument (tree or q)");
+        return NBKD_EINVAL;
+    }
+    if (!out_phi && !out_acc) {
+        set_error("nbkd_gravity: out_phi and out_acc are both NULL");
+        return NBKD_EINVAL;
+    }
+    if (!(theta >= 0.0f) || !(theta < 1.0f)) {
+        set_error("nbkd_gravity: the opening angle theta must be in [0, 1)");
+        return NBKD_EINVAL;
+    }
+    if (!(eps >= 0.0f) || !(eps <= FLT_MAX)) {
+        set_error("nbkd_gravity: the softening eps is NaN, infinite or negative");
+        return NBKD_EINVAL;
+    }
+    if (m >= (1ull << 32)) {
+        set_error("more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) return NBKD_OK;
+    if (tree->t.periodic) {
+        set_error("nbkd_gravity: the tree is periodic; Ewald sums are not provided");
+        return NBKD_EINVAL;
+    }
+    DeviceGuard g(tree->t.device);
+    return query_gravity(tree->t, q, m, mass, theta, eps, out_phi, out_acc, flags,
+                         (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_fof(const nbkd_tree *tree, float b, uint32_t *out_label, uint32_t *out_size,
                      uint64_t *out_ngroups, uint32_t flags, void *stream) {
     NBKD_GUARD_BEGIN

@@ -26,6 +26,8 @@ enum WsSlot {
     // nbkd_query_ball_sum: the values in tree order, the uploaded host values,
     // a host batch's radii
     WS_VT, WS_VALS, WS_HRAD,
+    // nbkd_gravity: the per-node moments (gravity.hip)
+    WS_GRAV,
     // host-buffer pipeline (query.hip host_pipeline): two slots of queries and
     // of up to two result arrays
     WS_HQ0, WS_HQ1, WS_HO00, WS_HO01, WS_HO10, WS_HO11, WS_NSLOTS
@@ -432,6 +434,18 @@ void launch_ball_sum_outside_dev(const Tree &t, const float *q, const float *h,
                                  int nv, int kernel, float *out_sum, uint32_t *out_count,
                                  hipStream_t s);
 
+// gravity.hip: Barnes-Hut potentials and accelerations (nbkd_gravity).
+// The moments pass fills `scratch` (gravity_scratch_bytes(t) bytes) from the
+// masses in tree order (mt, launch_ball_sum_gather with nv = 1) and returns the
+// per-node record table inside it; the walk answers m kd-ordered device queries
+// from that table (th2 = theta*theta, eps2 = eps*eps; out_phi (m,) and out_acc
+// (m, 3) device arrays, either may be nullptr)
+size_t gravity_scratch_bytes(const Tree &t);
+const void *launch_gravity_moments(const Tree &t, const float *mt, void *scratch, hipStream_t s);
+void launch_gravity_walk(const Tree &t, const void *rec, const float *q, const uint32_t *order,
+                         uint32_t m, const float *mt, float th2, float eps2, float *out_phi,
+                         float *out_acc, hipStream_t s);
+
 // per-row sort of a CSR batch (row offsets `off`, nrows + 1 entries, device):
 // rows of up to csr_sort_row_cap() ids in place; longer rows are appended to
 // long_rows (count in *nlong, zeroed by the caller) for the caller to sort
@@ -459,6 +473,12 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
 nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const float *h,
                            const float *values, int nv, int kernel, float *out_sum,
                            uint32_t *out_count, uint32_t flags, hipStream_t s);
+
+// mass: on q's side or nullptr (mass 1); theta, eps, the NULL cases and the
+// periodic tree checked by the caller (api.cpp); m > 0
+nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float *mass,
+                          float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
+                          hipStream_t s);
 
 // fof.hip: friends-of-friends groups of the tree's own points (b finite and
 // >= 0, out_label != nullptr: checked by the caller, api.cpp)

@@ -7,7 +7,7 @@
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
 // (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
-// (ball_sum), fof_labels, group_moments and export() for parity tests.
+// (ball_sum), gravity, fof_labels, group_moments and export() for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
 // kdtree/src/cpp/kdtree.cpp:116).  Queries release the GIL, may be called from
@@ -240,6 +240,47 @@ class PyKDTree {
         return py::make_tuple(sums, counts);
     }
 
+    // Barnes-Hut potentials and accelerations at the query points, G = 1
+    // (nbkd_gravity): (phi float32 (m,) or None, acc float32 (m, 3) or None).
+    // mass: None (mass 1) or an (N,) array by input row.
+    py::tuple gravity(farray points, std::optional<farray> mass, float theta, float eps,
+                      bool potential, bool acceleration) {
+        check_shape(points);
+        const py::ssize_t m = points.shape(0);
+        const float *w = nullptr;
+        if (mass.has_value()) {
+            if (mass->ndim() != 1 || (uint64_t)mass->shape(0) != n_in_)
+                throw std::runtime_error("mass must be a 1D array with one mass per point");
+            w = mass->data();
+        }
+        if (!potential && !acceleration)
+            throw std::runtime_error("at least one of potential and acceleration is needed");
+        py::object phi = py::none(), acc = py::none();
+        float *pp = nullptr, *ap = nullptr;
+        if (potential) {
+            py::array_t<float> arr(m);
+            pp = arr.mutable_data();
+            phi = arr;
+        }
+        if (acceleration) {
+            py::array_t<float> arr({m, (py::ssize_t)3});
+            ap = arr.mutable_data();
+            acc = arr;
+        }
+        const float *q = points.data();
+        // (m == 0: no array to point at; the library returns at once)
+        const float dummy[3] = {0.0f, 0.0f, 0.0f};
+        if (m == 0) q = dummy;
+        nbkd_status st;
+        Interruptible intr;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_gravity(h_, q, (uint64_t)m, w, theta, eps, pp, ap, 0u, nullptr);
+        }
+        intr.finish(st);
+        return py::make_tuple(phi, acc);
+    }
+
     // friends-of-friends groups of the tree's points (nbkd_fof): (labels uint32
     // (N,) = the smallest input row of each point's group, sizes uint32 (N,) =
     // the member count at each label, 0 elsewhere)
@@ -384,6 +425,9 @@ PYBIND11_MODULE(_impl, m) {
         .def("ball_sum", &PyKDTree::ball_sum, py::arg("points"), py::arg("h"),
              py::arg("values") = std::nullopt, py::arg("kernel") = NBKD_KERNEL_CUBIC,
              py::arg("count") = false)
+        .def("gravity", &PyKDTree::gravity, py::arg("points"), py::arg("mass") = std::nullopt,
+             py::arg("theta") = 0.5f, py::arg("eps") = 0.0f, py::arg("potential") = true,
+             py::arg("acceleration") = true)
         .def("fof_labels", &PyKDTree::fof_labels, py::arg("b"))
         .def("group_moments", &PyKDTree::group_moments, py::arg("labels"),
              py::arg("min_members") = 1, py::arg("weight") = std::nullopt,

@@ -1921,6 +1921,90 @@ nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const floa
     return NBKD_OK;
 }
 
+// the potentials and accelerations of m device queries into device outputs
+// (either may be nullptr); rec = the node moments, mt = the masses in tree order
+static nbkd_status gravity_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
+                                  const void *rec, const float *mt, float th2, float eps2,
+                                  float *out_phi, float *out_acc, uint32_t flags, hipStream_t s) {
+    if (m == 0) return NBKD_OK;
+    const uint32_t mm = (uint32_t)m;
+    uint32_t *ord = nullptr;
+    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
+                                                : sort_queries(t, ws, q, mm, ord, s);
+    if (rc) return rc;
+    TimedScope ts("gravity_walk", s);
+    launch_gravity_walk(t, rec, q, ord, mm, mt, th2, eps2, out_phi, out_acc, s);
+    NBKD_HIP(hipGetLastError());
+    return NBKD_OK;
+}
+
+nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float *mass,
+                          float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
+                          hipStream_t s) {
+    Workspace &ws = acquire_ws(t);
+    WsCall call(ws, s, std::adopt_lock);
+    NBKD_HIP(call.err);
+    const bool in_dev = (flags & NBKD_INPUT_DEVICE) != 0;
+    const bool out_dev = (flags & NBKD_OUTPUT_DEVICE) != 0;
+    if (t.n == 0 || t.nnodes == 0) {
+        // no point, no term
+        if (out_dev) {
+            if (out_phi) NBKD_HIP(hipMemsetAsync(out_phi, 0, (size_t)m * 4, s));
+            if (out_acc) NBKD_HIP(hipMemsetAsync(out_acc, 0, (size_t)m * 12, s));
+        } else {
+            if (out_phi) std::fill(out_phi, out_phi + m, 0.0f);
+            if (out_acc) std::fill(out_acc, out_acc + 3 * m, 0.0f);
+        }
+        return NBKD_OK;
+    }
+    // the masses once per call: uploaded when they are host memory, gathered
+    // into tree order (mt[p] = mass[row(p)], 1 without masses, 0 at the padding
+    // positions), then the node moments from them
+    const float *dmass = mass;
+    if (mass && !in_dev) {
+        const size_t vb = (size_t)t.n * 4;
+        float *up = (float *)ws.get(WS_VALS, vb, s);
+        if (!up) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemcpyAsync(up, mass, vb, hipMemcpyHostToDevice, s));
+        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
+        dmass = up;
+    }
+    float *mt = (float *)ws.get(WS_VT, (size_t)t.n8 * 4, s);
+    void *scratch = ws.get(WS_GRAV, gravity_scratch_bytes(t), s);
+    if (!mt || !scratch) return NBKD_ENOMEM;
+    const void *rec = nullptr;
+    {
+        TimedScope ts("gravity_moments", s);
+        launch_ball_sum_gather(t, dmass, 1, mt, s);
+        rec = launch_gravity_moments(t, mt, scratch, s);
+        NBKD_HIP(hipGetLastError());
+    }
+    const float th2 = theta * theta, eps2 = eps * eps;
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    if ((flags & dev_io) == dev_io)
+        return gravity_common(t, ws, q, m, rec, mt, th2, eps2, out_phi, out_acc, flags, s);
+    size_t ob[2];
+    void *outs[2];
+    int nout = 0;
+    const int iphi = out_phi ? nout : -1;
+    if (out_phi) {
+        ob[nout] = 4;
+        outs[nout++] = out_phi;
+    }
+    const int iacc = out_acc ? nout : -1;
+    if (out_acc) {
+        ob[nout] = 12;
+        outs[nout++] = out_acc;
+    }
+    return host_pipeline(
+        ws, q, m, flags, nout, ob, outs, 40,
+        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
+            return gravity_common(t, ws, dq, nb, rec, mt, th2, eps2,
+                                  iphi >= 0 ? (float *)o[iphi] : nullptr,
+                                  iacc >= 0 ? (float *)o[iacc] : nullptr, flags | dev_io, st);
+        }, s);
+}
+
 // the radius histogram of m device queries: rows into the device array
 // out_counts (or nullptr), column sums added to the device counters tot (or
 // nullptr)

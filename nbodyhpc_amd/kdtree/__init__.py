@@ -14,7 +14,8 @@ groups of the tree's points), ``fof_catalog`` (members, mass, centre, extent
 and value moments per group, reduced on the GPU), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
 ``interpolate`` (kernel-weighted sums over each query's own ball: the gather
-form of SPH), a ``device`` keyword, and
+form of SPH), ``gravity`` / ``potential`` (Barnes-Hut potentials and
+accelerations from the tree's points as masses), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
 no pickle inside) and pickling.  A restored tree is rebuilt on the GPU from
 the saved points (the build is deterministic: same node table; ~55 ms at 1e8),
@@ -405,6 +406,69 @@ class KDTree(cKDTree):
         with np.errstate(divide="ignore", invalid="ignore"):
             out = s[..., :-1] / s[..., -1:]
         return out[..., 0] if f.ndim == 1 else out
+
+    # ---------------------------------------------------------------- gravity
+    def gravity(self, points: Optional[np.ndarray] = None, mass=None, softening: float = 0.0,
+                theta: float = 0.5, G: float = 1.0, potential: bool = True,
+                acceleration: bool = True):
+        """Gravitational potential and acceleration at each query point from
+        the tree's points as masses, by a Barnes-Hut walk on the GPU:
+        ``phi_i = -G sum_j m_j / sqrt(d_ij^2 + softening^2)`` and
+        ``acc_i = G sum_j m_j (p_j - q_i) / (d_ij^2 + softening^2)^(3/2)``.
+
+        points : (..., 3) query points, or None: the tree's own points.
+        mass : (N,) masses indexed like the tree's input points, finite and
+            >= 0, or None (unit masses).
+        softening : the Plummer softening length, finite and >= 0.  A point at
+            the query's own position adds nothing, whatever the softening.
+        theta : the opening angle in [0, 1).  A node whose box diagonal is at
+            most theta times the distance to its centre of mass counts as one
+            mass there; 0 is the direct sum over all points.
+        G : scales both results (the device sums with G = 1).
+
+        Returns ``(phi, acc)``: float64 arrays of shape points.shape[:-1] and
+        points.shape[:-1] + (3,); the one switched off by ``potential=False``
+        or ``acceleration=False`` is None.  The device sums in float32, one
+        accumulator per query and component in an order fixed by the tree and
+        the query: identical calls give identical arrays, whatever else is
+        asked in the same call.  Periodic trees are not supported (no Ewald
+        sum)."""
+        w = None
+        if mass is not None:
+            w = np.asarray(mass, dtype=np.float32)
+            if w.shape != (self._n_input,):
+                raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point "
+                                 f"count, got {w.shape}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("every mass must be finite and >= 0")
+            w = np.ascontiguousarray(w)
+        th = float(theta)
+        if not 0.0 <= th < 1.0 or not np.float32(th) < np.float32(1.0):
+            raise ValueError(f"theta must be in [0, 1), got {theta!r}")
+        eps = float(softening)
+        with np.errstate(over="ignore"):
+            eps_ok = math.isfinite(eps) and eps >= 0.0 and bool(np.isfinite(np.float32(eps)))
+        if not eps_ok:
+            raise ValueError(f"softening must be finite and >= 0, got {softening!r}")
+        if not (potential or acceleration):
+            raise ValueError("at least one of potential and acceleration is needed")
+        if self.periodic:
+            raise ValueError("gravity needs a non-periodic tree: Ewald sums are not provided")
+        if points is None:
+            points = self.points()
+        points, shape = _flatten(points)
+        out_shape = tuple(shape[:-1]) if shape is not None else (np.asarray(points).shape[0],)
+        phi, acc = super().gravity(points, w, th, eps, bool(potential), bool(acceleration))
+        if phi is not None:
+            phi = (float(G) * phi.astype(np.float64)).reshape(out_shape)
+        if acc is not None:
+            acc = (float(G) * acc.astype(np.float64)).reshape(out_shape + (3,))
+        return phi, acc
+
+    def potential(self, points: Optional[np.ndarray] = None, mass=None, softening: float = 0.0,
+                  theta: float = 0.5, G: float = 1.0):
+        """The potential alone: ``gravity(..., acceleration=False)[0]``."""
+        return self.gravity(points, mass, softening, theta, G, True, False)[0]
 
     # ---------------------------------------------------------------- persistence
     def points(self) -> np.ndarray:
