@@ -383,6 +383,78 @@ nbkd_status nbkd_group_catalog(const nbkd_tree *tree, const uint32_t *label,
                                uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): per-group potentials, the halo finder's
+ * third step: for every entry of a list of row groups the potential of its own
+ * group's other entries at its position (what unbinding needs), and per group
+ * the entry of lowest potential (the most-bound particle, the usual halo
+ * centre).  A segmented direct sum, one call for all groups; G = 1.
+ *   offsets   (ngroups+1,) uint64 and
+ *   members   (nmembers,) uint32: members[offsets[g] : offsets[g+1]] = the input
+ *             rows of group g, as nbkd_group_catalog writes them.  Any grouping
+ *             is accepted: the groups need not be FoF groups, rows may be
+ *             missing and rows may repeat, so a list trimmed by the caller (a
+ *             round of unbinding) goes straight back in.
+ *   mass      (n,) float32 by input row (the build's permutation, also after
+ *             nbkd_set_ids), or NULL: mass 1.  Masses must be finite and >= 0;
+ *             otherwise the values are unspecified, but nothing faults.
+ *             offsets, members and mass are on one side: host, or device with
+ *             NBKD_INPUT_DEVICE
+ *   eps       the softening length, finite and >= 0
+ *   max_members  0: no limit.  Otherwise a group with more than max_members
+ *             entries is skipped: its out_phi entries are quiet NaNs and its
+ *             out_minpos is 0xFFFFFFFF.  The work is the sum over the groups of
+ *             s*s terms (s = the group's entry count): one group of 1e6 entries
+ *             is 1e12 terms.  Callers who cannot bound s should set max_members.
+ *   out_phi   (nmembers,) float32, aligned with members, or NULL
+ *   out_minpos (ngroups,) uint32, or NULL; at least one of the two; both host
+ *             memory, or both device memory with NBKD_OUTPUT_DEVICE
+ * Definition.  Entry e lies in group g when offsets[g] <= e < offsets[g+1];
+ * i = members[e].  Everything is float32 without fused multiply-adds unless
+ * float64 is stated.  acc64 = 0.0; for f = offsets[g] .. offsets[g+1]-1 in
+ * ascending order, j = members[f]:
+ *   d2 = the tree's metric between p_i and p_j (the kNN metric): d = p_j - p_i
+ *        per axis, on a periodic tree the minimum over |d|, |d - L|, |d + L|
+ *        per axis, then d2 = (d.x*d.x + d.y*d.y) + d.z*d.z;
+ *   d2 == 0 adds nothing (the entry itself, a repeated row, any coincident
+ *        point, for every eps); otherwise
+ *   r2 = d2 + eps*eps;  inv = 1.0f / sqrtf(r2);  acc64 += (double)(m_j*inv).
+ * out_phi[e] = (float)(-acc64).
+ * This is the isolated potential of the group under the minimum image.  On a
+ * periodic tree it is meaningful for groups with dmax < L/2 (nbkd_group_catalog's
+ * out_dmax: the group does not span the box); no Ewald sum is involved.
+ * out_minpos[g] = the smallest e of group g with the lowest out_phi[e], compared
+ * as the float32 values written (-0 and +0 are equal), so an argmin over
+ * out_phi[offsets[g] : offsets[g+1]] on the host gives the same entry; its row
+ * is members[out_minpos[g]].  Empty groups and skipped groups get 0xFFFFFFFF.
+ * Deterministic: one lane sums one entry into one float64 accumulator in list
+ * order; there are no floating-point atomics (the minimum is a 64-bit integer
+ * atomic over an order-preserving key, which commutes).  The result depends on
+ * the points, the masses, the list and eps only: not on the tree's leaf size,
+ * the launch geometry or timing.  Two calls give arrays equal under ==, and so
+ * do trees built from the same points with different leaf_size.
+ * NBKD_EINVAL before any device call, outputs untouched: NULL tree, offsets or
+ * members; both outputs NULL; eps NaN, negative or infinite; ngroups or
+ * nmembers >= 2^32.  ngroups == 0 is NBKD_OK and writes nothing; nmembers == 0
+ * is NBKD_OK: every group is empty, out_minpos is all 0xFFFFFFFF.  Otherwise a
+ * device kernel counts the violations of offsets[0] == 0, offsets
+ * non-decreasing, offsets[ngroups] == nmembers and members[e] < n before
+ * anything else runs: a nonzero count is NBKD_EINVAL with a message that gives
+ * the count, and no output is written; no kernel indexes with an unchecked row
+ * or offset.  The call always waits (the violation count is read on the host,
+ * as in nbkd_group_catalog).
+ * Scratch: 16 bytes per entry (x, y, z, m packed in list order), 4 bytes per
+ * entry (the entry's group number), 4 bytes per point (row -> tree position),
+ * 8 bytes per group (the argmin key), the uploaded host inputs and the staged
+ * host outputs (4 bytes per entry also when out_phi is NULL).
+ */
+nbkd_status nbkd_group_potential(const nbkd_tree *tree,
+                                 const uint64_t *offsets, const uint32_t *members,
+                                 uint64_t ngroups, uint64_t nmembers,
+                                 const float *mass, float eps, uint32_t max_members,
+                                 float *out_phi, uint32_t *out_minpos,
+                                 uint32_t flags, void *stream);
+
+/*
  * NEW: neighbour lists within r in CSR form.  out_offsets is (m+1,) uint64
  * (always host memory); out_idx receives offsets[m] original point indices,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row

@@ -59,6 +59,8 @@ _PROTOS = {
     "nbkd_group_catalog": (_i32, [_c_p, _c_p, _c_p, _c_p, _i32, _u32, _u64, _u64,
                                   ctypes.POINTER(_u64), ctypes.POINTER(_u64), _c_p, _c_p, _c_p,
                                   _c_p, _c_p, _c_p, _u32, _c_p]),
+    "nbkd_group_potential": (_i32, [_c_p, _c_p, _c_p, _u64, _u64, _c_p, ctypes.c_float, _u32,
+                                    _c_p, _c_p, _u32, _c_p]),
     "nbkd_tree_info": (_i32, [_c_p, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                               ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_float),
                               ctypes.POINTER(_i32)]),
@@ -396,6 +398,43 @@ class Tree:
                                         moments_ptr, dmax_ptr,
                                         NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
         return ng.value, nm.value
+
+    def group_potential(self, offsets, members, mass=None, eps=0.0, max_members=0, phi=True,
+                        minpos=True):
+        """nbkd_group_potential of host arrays, G = 1: (phi (K,) float32 or
+        None, minpos (ngroups,) uint32 or None).  offsets (ngroups + 1,) and
+        members (K,): the rows of each group (any grouping); mass: (n,) by
+        input row, or None (mass 1); max_members: larger groups are skipped
+        (NaN, 0xFFFFFFFF), 0 = no limit."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        mem = np.ascontiguousarray(members, dtype=np.uint32)
+        if off.ndim != 1 or off.shape[0] < 1 or mem.ndim != 1:
+            raise ValueError("offsets must be (ngroups + 1,) and members (K,)")
+        w = None
+        if mass is not None:
+            w = _host_f32(mass)
+            if w.shape != (self.npoints,):
+                raise ValueError("mass must be (n,) with n the tree's point count")
+        G, K = off.shape[0] - 1, mem.shape[0]
+        p = np.empty(K, np.float32) if phi else None
+        mp = np.empty(G, np.uint32) if minpos else None
+        # (K == 0: no array to point at; the library reads no member)
+        mptr = mem.ctypes.data if K else np.zeros(1, np.uint32).ctypes.data
+        _check(lib().nbkd_group_potential(self.h, off.ctypes.data, mptr, G, K,
+                                          None if w is None else w.ctypes.data, float(eps),
+                                          int(max_members), p.ctypes.data if phi else None,
+                                          mp.ctypes.data if minpos else None, 0, None))
+        return p, mp
+
+    def group_potential_device(self, offsets_ptr, members_ptr, ngroups, nmembers, mass_ptr, eps,
+                               max_members, phi_ptr, minpos_ptr=None, stream=None):
+        """Device offsets, members, masses ((n,) or None) and outputs ((K,)
+        float32 potentials and / or (ngroups,) uint32 entries); the call waits
+        (the violation count of the list is read on the host)."""
+        _check(lib().nbkd_group_potential(self.h, offsets_ptr, members_ptr, int(ngroups),
+                                          int(nmembers), mass_ptr, float(eps), int(max_members),
+                                          phi_ptr, minpos_ptr,
+                                          NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
 
     def ball_csr(self, q, r, sorted=False):
         """CSR radius query of host queries: (offsets (m + 1,) uint64, ids);

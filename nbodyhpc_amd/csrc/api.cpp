@@ -772,6 +772,50 @@ nbkd_status nbkd_group_catalog(const nbkd_tree *tree, const uint32_t *label,
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_group_potential(const nbkd_tree *tree, const uint64_t *offsets,
+                                 const uint32_t *members, uint64_t ngroups, uint64_t nmembers,
+                                 const float *mass, float eps, uint32_t max_members,
+                                 float *out_phi, uint32_t *out_minpos, uint32_t flags,
+                                 void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !offsets || !members) {
+        set_error("nbkd_group_potential: NULL argument (tree, offsets or members)");
+        return NBKD_EINVAL;
+    }
+    if (!out_phi && !out_minpos) {
+        set_error("nbkd_group_potential: out_phi and out_minpos are both NULL");
+        return NBKD_EINVAL;
+    }
+    if (!(eps >= 0.0f) || !(eps <= FLT_MAX)) {
+        set_error("nbkd_group_potential: the softening eps is NaN, infinite or negative");
+        return NBKD_EINVAL;
+    }
+    if (ngroups >= (1ull << 32) || nmembers >= (1ull << 32)) {
+        set_error("nbkd_group_potential: more than 2^32 - 1 groups or entries per call are not "
+                  "supported");
+        return NBKD_EINVAL;
+    }
+    if (ngroups == 0) return NBKD_OK;
+    if (nmembers == 0) { // every group is empty: no sum, no entry of lowest potential
+        if (out_minpos) {
+            if (flags & NBKD_OUTPUT_DEVICE) {
+                DeviceGuard g(tree->t.device);
+                hipStream_t s = (hipStream_t)stream;
+                NBKD_HIP(hipMemsetAsync(out_minpos, 0xFF, (size_t)ngroups * 4, s));
+                NBKD_HIP(hipStreamSynchronize(s));
+            } else {
+                std::fill(out_minpos, out_minpos + ngroups, 0xFFFFFFFFu);
+            }
+        }
+        return NBKD_OK;
+    }
+    DeviceGuard g(tree->t.device);
+    return group_potential(tree->t, offsets, members, ngroups, nmembers, mass, eps, max_members,
+                           out_phi, out_minpos, flags, (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_query_ball_csr(const nbkd_tree *tree, const float *q, uint64_t m, float r,
                                 uint64_t *out_offsets, uint32_t *out_idx, uint64_t capacity,
                                 uint32_t flags, void *stream) {

@@ -366,6 +366,12 @@ unsigned blocks_for(uint64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 } // namespace
 
+void launch_group_inv(const Tree &t, uint32_t *inv, hipStream_t s) {
+    if (t.n8 == 0) return;
+    const uint32_t *perm = t.sidx ? t.sidx : t.idx;
+    group_inv_kernel<<<blocks_for(t.n8), TB, 0, s>>>(perm, (uint32_t)t.n8, (uint32_t)t.n, inv);
+}
+
 nbkd_status group_catalog(const Tree &t, const uint32_t *label, const float *weight,
                           const float *values, int nv, uint32_t min_members,
                           uint64_t group_capacity, uint64_t member_capacity,

@@ -503,6 +503,18 @@ nbkd_status group_catalog(const Tree &t, const uint32_t *label, const float *wei
                           uint32_t *out_size, uint64_t *out_offsets, uint32_t *out_members,
                           double *out_moments, float *out_dmax, uint32_t flags, hipStream_t s);
 
+// group.hip: inv[row] = the tree position of input row `row` (n words; the
+// build's permutation scattered, also after nbkd_set_ids)
+void launch_group_inv(const Tree &t, uint32_t *inv, hipStream_t s);
+
+// group_potential.hip: per-entry potentials of a list of row groups and each
+// group's entry of lowest potential (the NULL cases, eps and the counts
+// checked by the caller, api.cpp; ngroups > 0 and nmembers > 0)
+nbkd_status group_potential(const Tree &t, const uint64_t *offsets, const uint32_t *members,
+                            uint64_t ngroups, uint64_t nmembers, const float *mass, float eps,
+                            uint32_t max_members, float *out_phi, uint32_t *out_minpos,
+                            uint32_t flags, hipStream_t s);
+
 // deposit.hip: spheres onto a voxel grid (render_points_volume / render_points)
 nbkd_status deposit(const float *xyz, const float *weight, const float *radius, uint64_t n, int gx,
                     int gy, int nz, float ppu, const float *period, int S, int mode, int x0, int wx,

@@ -7,7 +7,8 @@
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
 // (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
-// (ball_sum), gravity, fof_labels, group_moments and export() for parity tests.
+// (ball_sum), gravity, fof_labels, group_moments, group_potential and export()
+// for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
 // kdtree/src/cpp/kdtree.cpp:116).  Queries release the GIL, may be called from
@@ -360,6 +361,41 @@ class PyKDTree {
         return py::make_tuple(head, size, offsets, mem, mom, dmax);
     }
 
+    // per-entry potentials of a list of row groups and each group's entry of
+    // lowest potential (nbkd_group_potential): (phi float32 (K,), minpos uint32
+    // (G,), 0xFFFFFFFF for an empty or a skipped group)
+    py::tuple group_potential(
+        py::array_t<uint64_t, py::array::c_style | py::array::forcecast> offsets,
+        py::array_t<uint32_t, py::array::c_style | py::array::forcecast> members,
+        std::optional<farray> mass, float eps, uint32_t max_members) {
+        if (offsets.ndim() != 1 || offsets.shape(0) < 1)
+            throw std::runtime_error("offsets must be a 1D array of ngroups + 1 entries");
+        if (members.ndim() != 1) throw std::runtime_error("members must be a 1D array");
+        const float *w = nullptr;
+        if (mass.has_value()) {
+            if (mass->ndim() != 1 || (uint64_t)mass->shape(0) != n_in_)
+                throw std::runtime_error("mass must be a 1D array with one mass per point");
+            w = mass->data();
+        }
+        const py::ssize_t G = offsets.shape(0) - 1, K = members.shape(0);
+        py::array_t<float> phi(K);
+        py::array_t<uint32_t> minpos(G);
+        const uint64_t *op = offsets.data();
+        // (K == 0: no array to point at; the library reads no member)
+        const uint32_t dummy = 0;
+        const uint32_t *mp = K ? members.data() : &dummy;
+        float *pp = phi.mutable_data();
+        uint32_t *ip = minpos.mutable_data();
+        nbkd_status st;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_group_potential(h_, op, mp, (uint64_t)G, (uint64_t)K, w, eps, max_members,
+                                      pp, ip, 0u, nullptr);
+        }
+        check(st);
+        return py::make_tuple(phi, minpos);
+    }
+
     // rows sorted ascending on the device unless sorted=false (NBKD_SORTED);
     // both passes stream in batches and poll Ctrl-C between them
     std::pair<py::array_t<uint64_t>, py::array_t<uint32_t>> query_ball_csr(farray points, float r,
@@ -432,6 +468,9 @@ PYBIND11_MODULE(_impl, m) {
         .def("group_moments", &PyKDTree::group_moments, py::arg("labels"),
              py::arg("min_members") = 1, py::arg("weight") = std::nullopt,
              py::arg("values") = std::nullopt, py::arg("members") = true)
+        .def("group_potential", &PyKDTree::group_potential, py::arg("offsets"),
+             py::arg("members"), py::arg("mass") = std::nullopt, py::arg("eps") = 0.0f,
+             py::arg("max_members") = 0)
         .def("export", &PyKDTree::export_tree)
         .def_property_readonly("n", &PyKDTree::num_points)
         .def_property_readonly("size", &PyKDTree::num_nodes)

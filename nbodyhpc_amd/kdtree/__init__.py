@@ -15,7 +15,9 @@ and value moments per group, reduced on the GPU), ``density`` (local number dens
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
 ``interpolate`` (kernel-weighted sums over each query's own ball: the gather
 form of SPH), ``gravity`` / ``potential`` (Barnes-Hut potentials and
-accelerations from the tree's points as masses), a ``device`` keyword, and
+accelerations from the tree's points as masses), ``group_potential`` /
+``unbind`` (each group member's potential from its own group, the most-bound
+member, iterative unbinding), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
 no pickle inside) and pickling.  A restored tree is rebuilt on the GPU from
 the saved points (the build is deterministic: same node table; ~55 ms at 1e8),
@@ -469,6 +471,185 @@ class KDTree(cKDTree):
                   theta: float = 0.5, G: float = 1.0):
         """The potential alone: ``gravity(..., acceleration=False)[0]``."""
         return self.gravity(points, mass, softening, theta, G, True, False)[0]
+
+    # ---------------------------------------------------------------- group potentials
+    def _group_args(self, offsets, members, mass, softening, theta, max_direct):
+        """Checked arguments of ``group_potential`` / ``unbind``: (offsets
+        uint64 (G + 1,), members uint32 (K,), float32 masses (N,) or None,
+        eps, theta, max_direct).  Runs before any device call."""
+        n = self._n_input
+        off = np.asarray(offsets)
+        if off.ndim != 1 or off.shape[0] < 1 or off.dtype.kind not in "iu":
+            raise ValueError("offsets must be a 1-D integer array of ngroups + 1 entries, got "
+                             f"shape {off.shape}, dtype {off.dtype}")
+        mem = np.asarray(members)
+        if mem.ndim != 1 or (mem.size and mem.dtype.kind not in "iu"):
+            raise ValueError(f"members must be a 1-D integer array of rows, got shape {mem.shape}, "
+                             f"dtype {mem.dtype}")
+        off64 = off.astype(np.int64)
+        if off64[0] != 0 or off64[-1] != mem.shape[0] or np.any(off64[1:] < off64[:-1]):
+            raise ValueError("offsets must start at 0, never decrease and end at len(members) = "
+                             f"{mem.shape[0]}")
+        if mem.size and (int(mem.min()) < 0 or int(mem.max()) >= n):
+            raise ValueError(f"members must be rows in [0, N) with N = {n} the tree's point count")
+        w = None
+        if mass is not None:
+            w = np.asarray(mass, dtype=np.float32)
+            if w.shape != (n,):
+                raise ValueError(f"mass must be (N,) with N = {n} the tree's point count, got "
+                                 f"{w.shape}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("every mass must be finite and >= 0")
+            w = np.ascontiguousarray(w)
+        eps = float(softening)
+        with np.errstate(over="ignore"):
+            eps_ok = math.isfinite(eps) and eps >= 0.0 and bool(np.isfinite(np.float32(eps)))
+        if not eps_ok:
+            raise ValueError(f"softening must be finite and >= 0, got {softening!r}")
+        th = float(theta)
+        if not 0.0 <= th < 1.0 or not np.float32(th) < np.float32(1.0):
+            raise ValueError(f"theta must be in [0, 1), got {theta!r}")
+        if max_direct is not None:
+            if int(max_direct) != max_direct or not 1 <= int(max_direct) < 2 ** 32:
+                raise ValueError(f"max_direct must be None or an integer in [1, 2^32), got "
+                                 f"{max_direct!r}")
+            max_direct = int(max_direct)
+        return (np.ascontiguousarray(off64.astype(np.uint64)),
+                np.ascontiguousarray(mem, dtype=np.uint32), w, eps, th, max_direct)
+
+    def _unwrapped(self, rows, pts):
+        """float32 positions of ``rows`` relative to the first of them; on a
+        periodic tree each axis takes the image nearest to it (the catalogue's
+        rule: of d, d - L, d + L the smallest magnitude, ties to the earlier)."""
+        d = pts[rows] - pts[rows[0]]
+        if self.periodic:
+            L = np.float32(self.boxsize)
+            for alt in (d - L, d + L):
+                closer = np.abs(alt) < np.abs(d)
+                d = np.where(closer, alt, d)
+        return np.ascontiguousarray(d, dtype=np.float32)
+
+    def _group_phi(self, off, mem, w, eps, th, G, max_direct, pts=None):
+        """(phi float64 (K,), most_bound int64 (G,), the cached points)."""
+        phi32, minpos = super().group_potential(off, mem, w, eps, max_direct or 0)
+        phi = float(G) * phi32.astype(np.float64)
+        most = np.full(minpos.shape[0], -1, np.int64)
+        has = minpos != np.uint32(0xFFFFFFFF)
+        most[has] = mem[minpos[has]]
+        if max_direct is not None:
+            o = off.astype(np.int64)
+            for g in np.flatnonzero(np.diff(o) > max_direct):
+                if pts is None:
+                    pts = self.points()
+                rows = mem[o[g]:o[g + 1]]
+                tmp = KDTree(self._unwrapped(rows, pts), self._leafsize)
+                pg = tmp.potential(None, None if w is None else w[rows], eps, th, G)
+                phi[o[g]:o[g + 1]] = pg
+                most[g] = rows[int(np.argmin(pg))]
+        return phi, most, pts
+
+    def group_potential(self, offsets, members, mass=None, softening: float = 0.0,
+                        G: float = 1.0, max_direct: Optional[int] = 200_000, theta: float = 0.5):
+        """The potential of every member from its own group only, and each
+        group's most-bound member: ``phi_e = -G sum_f m_j / sqrt(d_ij^2 +
+        softening^2)`` over the entries f of e's group (i = members[e],
+        j = members[f]), a direct sum on the GPU in one call for all groups.
+
+        offsets, members : ``members[offsets[g]:offsets[g + 1]]`` = the rows of
+            group g, as ``fof_catalog(..., members=True)`` returns them.  Any
+            grouping is accepted: rows may be missing or repeat, groups may be
+            empty, so a trimmed list (``unbind``) goes straight back in.
+        mass : (N,) masses indexed like the tree's input points, finite and
+            >= 0, or None (unit masses).
+        softening : the Plummer softening length.  The entry itself, a repeated
+            row and a coincident point add nothing, whatever the softening.
+        max_direct : groups with more entries are not summed directly (the work
+            is the square of the size): each is unwrapped relative to its first
+            member, put into a temporary non-periodic tree and answered by
+            ``potential(theta=theta)``.  Their values are approximate (the
+            Barnes-Hut error of ``theta``; float32 accumulation), and their
+            most-bound member is the argmin of those values.  None sums every
+            group directly.  The default bounds one group's direct sum to about
+            50 ms (4e10 terms at the 8e11 terms per second DESIGN.md records).
+
+        On a periodic tree distances are minimum-image ones: the isolated
+        potential of the group, meaningful for groups that do not span the box
+        (``spans_box`` False).  The device forms each term in float32 and sums
+        a member's terms in float64 in list order: identical calls give
+        identical arrays, independent of the tree's leaf size.
+
+        Returns ``(phi, most_bound)``: float64 (K,) aligned with ``members``,
+        and int64 (G,), the row of the smallest entry with the lowest
+        potential, -1 for an empty group."""
+        off, mem, w, eps, th, md = self._group_args(offsets, members, mass, softening, theta,
+                                                    max_direct)
+        phi, most, _ = self._group_phi(off, mem, w, eps, th, G, md)
+        return phi, most
+
+    def unbind(self, offsets, members, velocities, mass=None, softening: float = 0.0,
+               G: float = 1.0, max_iter: int = 20, min_members: int = 1,
+               max_direct: Optional[int] = 200_000, theta: float = 0.5):
+        """Iterative unbinding of a list of groups.  Each iteration computes,
+        per group, the mass-weighted mean velocity of the current members (in
+        float64) and ``E = |v - vbar|^2 / 2 + phi`` with ``phi`` from
+        ``group_potential`` (same arguments); every member with E >= 0 is
+        dropped (order kept), and a group left with fewer than ``min_members``
+        members is emptied.  It stops when an iteration drops nothing, or after
+        ``max_iter`` iterations.
+
+        velocities : (N, 3) indexed like the tree's input points.
+
+        Returns a dict: ``offsets`` uint64 (G + 1,) (the same G: an emptied
+        group has equal offsets) and ``members`` uint32, the bound members;
+        ``phi`` and ``energy`` float64, of that final state and aligned with
+        ``members``; ``most_bound`` int64 (G,) (-1 for an empty group);
+        ``iterations``, the number of iterations run (the last one, which
+        dropped nothing, included)."""
+        off, mem, w, eps, th, md = self._group_args(offsets, members, mass, softening, theta,
+                                                    max_direct)
+        n = self._n_input
+        vel = np.asarray(velocities, dtype=np.float64)
+        if vel.shape != (n, 3):
+            raise ValueError(f"velocities must be (N, 3) with N = {n} the tree's point count, got "
+                             f"{vel.shape}")
+        if int(max_iter) < 0:
+            raise ValueError(f"max_iter must be >= 0, got {max_iter!r}")
+        min_members = max(int(min_members), 1)
+        w64 = np.ones(n, np.float64) if w is None else w.astype(np.float64)
+        ngroups = off.shape[0] - 1
+        pts, iterations = None, 0
+        while True:
+            phi, most, pts = self._group_phi(off, mem, w, eps, th, G, md, pts)
+            o = off.astype(np.int64)
+            cnt = np.diff(o)
+            full = np.flatnonzero(cnt > 0)
+            starts = o[:-1][full]  # strictly ascending: reduceat sums exactly these groups
+            gid = np.repeat(np.arange(ngroups), cnt)
+            mm, vv = w64[mem], vel[mem]
+            vbar = np.zeros((ngroups, 3))
+            if full.size:
+                msum = np.add.reduceat(mm, starts)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    vb = np.add.reduceat(mm[:, None] * vv, starts, axis=0) / msum[:, None]
+                plain = np.add.reduceat(vv, starts, axis=0) / cnt[full][:, None]
+                vbar[full] = np.where(msum[:, None] > 0, vb, plain)  # (massless group: plain mean)
+            dv = vv - vbar[gid]
+            energy = 0.5 * np.sum(dv * dv, axis=1) + phi
+            if iterations >= int(max_iter):
+                break
+            iterations += 1
+            keep = ~(energy >= 0.0)
+            left = np.zeros(ngroups, np.int64)
+            if full.size:
+                left[full] = np.add.reduceat(keep.astype(np.int64), starts)
+            keep &= (left >= min_members)[gid]
+            if keep.all():
+                break
+            left = np.where(left >= min_members, left, 0)
+            mem = np.ascontiguousarray(mem[keep])
+            off = np.concatenate([[0], np.cumsum(left)]).astype(np.uint64)
+        return {"offsets": off, "members": mem, "phi": phi, "energy": energy,
+                "most_bound": most, "iterations": iterations}
 
     # ---------------------------------------------------------------- persistence
     def points(self) -> np.ndarray:
