@@ -244,6 +244,62 @@ nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t 
                                 uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): weighted radial profiles around each query
+ * in one tree walk: the mass (or any per-particle channel) in nr shells, with
+ * the shell edges shared by all queries or in units of each query's own scale.
+ * What spherical-overdensity masses and radii (M200c, R200c), stacked profiles
+ * and concentrations are read from; with the tree's points as queries, the
+ * weighted pair counts of a marked correlation function.
+ *   q          (m, 3) float32
+ *   scale      (m,) float32 on the same side as q (both host, or both device
+ *              with NBKD_INPUT_DEVICE), or NULL
+ *   radii      (nr,) float32, host memory, ascending (equal neighbours allowed),
+ *              each finite and >= 0, 1 <= nr <= NBKD_MAX_RADII: the conditions
+ *              of nbkd_query_ball_hist
+ *   values     (n, nv) row-major float32 on the same side as q, indexed by input
+ *              row (the build's permutation, also after nbkd_set_ids), or NULL:
+ *              weight 1, nv must then be 1.  1 <= nv <= NBKD_MAX_VALUES.
+ *   out_sum    (m, nr, nv) row-major float32, required; host, or device with
+ *              NBKD_OUTPUT_DEVICE
+ * Edges and thresholds of query i, in float32: e_ik = fl(radii[k] * scale[i]),
+ * or radii[k] when scale == NULL; t_ik = fl(e_ik * e_ik), a product that
+ * overflows counts as FLT_MAX (nbkd_query_ball_sum's rule).  Rounding is
+ * monotone, so the t_ik are non-decreasing in k.  A query whose scale is NaN,
+ * infinite or negative has an empty row (all zeros); scale 0 reaches coincident
+ * points only (bin 0).
+ * Point j falls into bin b = #{k : !(d2(i, j) <= t_ik)}, with d2 the tree's
+ * float32 metric: the test of nbkd_query_ball_count.  b == nr means the point
+ * is outside and added nowhere.  Padding points are in no bin.
+ * out_sum[i, b, c] = sum_j values[j, c] over the points of bin b.  The result
+ * is per-bin, not cumulative: a cumulative sum belongs to the caller, in
+ * float64.  With values == NULL and scale == NULL the running sum over b of row
+ * i (exact: integers below 2^24) equals row i of nbkd_query_ball_hist at the
+ * same radii.
+ * Deterministic: there are no floating-point atomics; each (i, b, c) is summed
+ * by one lane into one float32 accumulator in the tree's traversal order (a
+ * periodic query outside [0, L]^3 by a fixed-order reduction over all points),
+ * without fused multiply-adds (there is no product), so two identical calls
+ * give arrays that are equal under ==.  As with nbkd_query_ball_sum, a call
+ * whose queries are the tree's build array (the self-order path), one with
+ * other queries and other host batch sizes may differ in the last bits of a
+ * sum, never in which points a bin holds.
+ * NBKD_EINVAL before any device call, outputs untouched: NULL tree, q, radii or
+ * out_sum; nr or nv out of range; values == NULL with nv != 1; radii not
+ * ascending, not finite or negative; m >= 2^32.  m == 0 is NBKD_OK.  With
+ * device inputs and outputs the call returns once the work is enqueued, as
+ * nbkd_query_ball_sum does.  Host arrays stream in batches (see above), each
+ * batch's slice of scale with its queries; values are uploaded once per call.
+ * Scratch: 4 nv bytes per point of the call's workspace (the values in tree
+ * order).
+ */
+nbkd_status nbkd_query_ball_profile(const nbkd_tree *tree, const float *q, uint64_t m,
+                                    const float *scale,             /* (m,) or NULL          */
+                                    const float *radii, int32_t nr, /* host, ascending       */
+                                    const float *values, int32_t nv,
+                                    float *out_sum,                 /* (m, nr, nv) row-major */
+                                    uint32_t flags, void *stream);
+
+/*
  * NEW (no reference counterpart): Barnes-Hut potentials and accelerations at
  * m query points from the tree's points as masses, G = 1 (the caller scales),
  * Plummer softening eps: what unbinding, the most-bound particle and a force

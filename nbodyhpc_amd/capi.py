@@ -24,6 +24,7 @@ NBKD_SORTED = 0x10
 # nbkd_query_ball_sum kernels and channel limit
 KERNEL_TOPHAT, KERNEL_CUBIC, KERNEL_WENDLAND = 0, 1, 2
 NBKD_MAX_VALUES = 4
+NBKD_MAX_RADII = 32
 
 NODE_DTYPE = np.dtype([("dim", "<i4"), ("split", "<f4"), ("left", "<u4"), ("right", "<u4")])
 
@@ -51,6 +52,8 @@ _PROTOS = {
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_ball_sum": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _u32,
                                    _c_p]),
+    "nbkd_query_ball_profile": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _c_p, _i32, _c_p, _u32,
+                                       _c_p]),
     "nbkd_gravity": (_i32, [_c_p, _c_p, _u64, _c_p, ctypes.c_float, ctypes.c_float, _c_p, _c_p,
                             _u32, _c_p]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
@@ -297,6 +300,45 @@ class Tree:
         _check(lib().nbkd_query_ball_sum(self.h, q_ptr, int(m), h_ptr, values_ptr, int(nv),
                                          int(kernel), sum_ptr, count_ptr,
                                          NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+
+    def ball_profile(self, q, radii, values=None, scale=None):
+        """nbkd_query_ball_profile of host arrays: the raw float32 per-bin sums,
+        (m, nr) without values or for 1-D values, else (m, nr, nv).  radii:
+        ascending, shared by the queries; scale: one factor per query or None
+        (edges radii[k] * scale[i]); values: (n,) or (n, nv) by input row."""
+        q = _host_f32(q).reshape(-1, 3)
+        m = q.shape[0]
+        r = _host_f32(radii).reshape(-1)
+        nr = r.shape[0]
+        sc = None
+        if scale is not None:
+            sc = _host_f32(scale).reshape(-1)
+            if sc.shape[0] != m:
+                raise ValueError("scale must hold one factor per query")
+        v, nv = None, 1
+        if values is not None:
+            v = _host_f32(values)
+            if v.ndim not in (1, 2) or v.shape[0] != self.npoints:
+                raise ValueError("values must be (n,) or (n, nv) with n the tree's point count")
+            nv = 1 if v.ndim == 1 else v.shape[1]
+        flat = v is None or v.ndim == 1
+        s = np.empty((m, nr) if flat else (m, nr, nv), np.float32)
+        _check(lib().nbkd_query_ball_profile(self.h, q.ctypes.data, m,
+                                             None if sc is None else sc.ctypes.data,
+                                             r.ctypes.data, nr,
+                                             None if v is None else v.ctypes.data, int(nv),
+                                             s.ctypes.data, 0, None))
+        return s
+
+    def ball_profile_device(self, q_ptr, m, radii, scale_ptr, values_ptr, nv, sum_ptr,
+                            stream=None):
+        """Device queries, scales ((m,) or None), values ((n, nv) or None) and
+        sums ((m, nr, nv) float32); the radii are host memory.  Returns once
+        enqueued."""
+        r = _host_f32(radii).reshape(-1)
+        _check(lib().nbkd_query_ball_profile(self.h, q_ptr, int(m), scale_ptr, r.ctypes.data,
+                                             r.shape[0], values_ptr, int(nv), sum_ptr,
+                                             NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
 
     def gravity(self, q, mass=None, theta=0.5, eps=0.0, phi=True, acc=True):
         """nbkd_gravity of host arrays, G = 1: (phi (m,) float32 or None, acc

@@ -679,6 +679,54 @@ nbkd_status nbkd_query_ball_sum(const nbkd_tree *tree, const float *q, uint64_t 
     NBKD_GUARD_END
 }
 
+nbkd_status nbkd_query_ball_profile(const nbkd_tree *tree, const float *q, uint64_t m,
+                                    const float *scale, const float *radii, int32_t nr,
+                                    const float *values, int32_t nv, float *out_sum,
+                                    uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q || !radii || !out_sum) {
+        set_error("nbkd_query_ball_profile: NULL argument (tree, q, radii or out_sum)");
+        return NBKD_EINVAL;
+    }
+    if (nr < 1 || nr > NBKD_MAX_RADII) {
+        set_error("nbkd_query_ball_profile: the number of radii must be in [1, " +
+                  std::to_string(NBKD_MAX_RADII) + "], got " + std::to_string(nr));
+        return NBKD_EINVAL;
+    }
+    if (nv < 1 || nv > NBKD_MAX_VALUES) {
+        set_error("nbkd_query_ball_profile: the number of value channels must be in [1, " +
+                  std::to_string(NBKD_MAX_VALUES) + "], got " + std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    if (!values && nv != 1) {
+        set_error("nbkd_query_ball_profile: values == NULL (weight 1) needs nv == 1, got " +
+                  std::to_string(nv));
+        return NBKD_EINVAL;
+    }
+    for (int32_t j = 0; j < nr; ++j) {
+        if (!(radii[j] >= 0.0f) || !(radii[j] <= FLT_MAX)) {
+            set_error("nbkd_query_ball_profile: radius " + std::to_string(j) +
+                      " is NaN, infinite or negative");
+            return NBKD_EINVAL;
+        }
+        if (j > 0 && radii[j] < radii[j - 1]) {
+            set_error("nbkd_query_ball_profile: the radii must be ascending (radius " +
+                      std::to_string(j) + " is below radius " + std::to_string(j - 1) + ")");
+            return NBKD_EINVAL;
+        }
+    }
+    if (m >= (1ull << 32)) {
+        set_error("more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) return NBKD_OK;
+    DeviceGuard g(tree->t.device);
+    return query_ball_profile(tree->t, q, m, scale, radii, nr, values, nv, out_sum, flags,
+                              (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
 nbkd_status nbkd_gravity(const nbkd_tree *tree, const float *q, uint64_t m, const float *mass,
                          float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
                          void *stream) {

@@ -434,6 +434,23 @@ void launch_ball_sum_outside_dev(const Tree &t, const float *q, const float *h,
                                  int nv, int kernel, float *out_sum, uint32_t *out_count,
                                  hipStream_t s);
 
+// ball_profile.hip: weighted radial profiles (nbkd_query_ball_profile).
+// R.r[0 .. nr) = the ascending radii (passed to the kernels by value); scale =
+// one factor per query (indexed by query id like q) or nullptr (1); vt as for
+// launch_ball_sum; out_sum (m, nr, nv) device array of per-bin sums.  Periodic
+// queries outside [0, L]^3 are skipped by the packet kernel and answered by the
+// second launch (list length in device memory).
+struct ProfRadii {
+    float r[NBKD_MAX_RADII];
+};
+void launch_ball_profile(const Tree &t, const float *q, const float *scale, const uint32_t *order,
+                         uint32_t m, const ProfRadii &R, int nr, const float *vt, int nv,
+                         float *out_sum, hipStream_t s);
+void launch_ball_profile_outside_dev(const Tree &t, const float *q, const float *scale,
+                                     const uint32_t *list, const uint32_t *nout,
+                                     const ProfRadii &R, int nr, const float *vt, int nv,
+                                     float *out_sum, hipStream_t s);
+
 // gravity.hip: Barnes-Hut potentials and accelerations (nbkd_gravity).
 // The moments pass fills `scratch` (gravity_scratch_bytes(t) bytes) from the
 // masses in tree order (mt, launch_ball_sum_gather with nv = 1) and returns the
@@ -473,6 +490,12 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
 nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const float *h,
                            const float *values, int nv, int kernel, float *out_sum,
                            uint32_t *out_count, uint32_t flags, hipStream_t s);
+
+// scale, values: on q's side or nullptr; radii: host, nr ascending, finite,
+// non-negative; nr, nv and the NULL cases checked by the caller (api.cpp); m > 0
+nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const float *scale,
+                               const float *radii, int nr, const float *values, int nv,
+                               float *out_sum, uint32_t flags, hipStream_t s);
 
 // mass: on q's side or nullptr (mass 1); theta, eps, the NULL cases and the
 // periodic tree checked by the caller (api.cpp); m > 0

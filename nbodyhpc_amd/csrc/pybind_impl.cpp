@@ -7,7 +7,7 @@
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
 // (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
-// (ball_sum), gravity, fof_labels, group_moments, group_potential and export()
+// (ball_sum), radial profiles (ball_profile), gravity, fof_labels, group_moments, group_potential and export()
 // for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
@@ -241,6 +241,55 @@ class PyKDTree {
         return py::make_tuple(sums, counts);
     }
 
+    // weighted radial profiles (nbkd_query_ball_profile): raw float32 per-bin
+    // sums (m, nr, nv).  values: None (weight 1, nv = 1) or an (N, nv) array by
+    // input row; scale: None or one factor per query.
+    py::array_t<float> ball_profile(farray points, farray radii, std::optional<farray> values,
+                                    std::optional<farray> scale) {
+        check_shape(points);
+        if (radii.ndim() != 1) throw std::runtime_error("radii must be a 1D array");
+        const py::ssize_t m = points.shape(0), nr = radii.shape(0);
+        if (nr < 1 || nr > NBKD_MAX_RADII)
+            throw std::runtime_error("the number of radii must be in [1, " +
+                                     std::to_string(NBKD_MAX_RADII) + "]");
+        const float *sc = nullptr;
+        if (scale.has_value()) {
+            if (scale->ndim() != 1 || scale->shape(0) != m)
+                throw std::runtime_error("scale must be a 1D array with one factor per query");
+            sc = scale->data();
+        }
+        py::ssize_t nv = 1;
+        const float *v = nullptr;
+        if (values.has_value()) {
+            if (values->ndim() != 2 || (uint64_t)values->shape(0) != n_in_)
+                throw std::runtime_error("values must be a 2D array of shape (N, nv)");
+            nv = values->shape(1);
+            v = values->data();
+        }
+        if (nv < 1 || nv > NBKD_MAX_VALUES)
+            throw std::runtime_error("the number of value channels must be in [1, " +
+                                     std::to_string(NBKD_MAX_VALUES) + "]");
+        py::array_t<float> sums({m, nr, nv});
+        const float *q = points.data(), *r = radii.data();
+        float *sp = sums.mutable_data();
+        // (m == 0: no arrays to point at; the library returns at once)
+        const float dummy[3] = {0.0f, 0.0f, 0.0f};
+        float dummy_out[1];
+        if (m == 0) {
+            q = dummy;
+            sp = dummy_out;
+        }
+        nbkd_status st;
+        Interruptible intr;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_query_ball_profile(h_, q, (uint64_t)m, sc, r, (int32_t)nr, v, (int32_t)nv,
+                                         sp, 0u, nullptr);
+        }
+        intr.finish(st);
+        return sums;
+    }
+
     // Barnes-Hut potentials and accelerations at the query points, G = 1
     // (nbkd_gravity): (phi float32 (m,) or None, acc float32 (m, 3) or None).
     // mass: None (mass 1) or an (N,) array by input row.
@@ -461,6 +510,8 @@ PYBIND11_MODULE(_impl, m) {
         .def("ball_sum", &PyKDTree::ball_sum, py::arg("points"), py::arg("h"),
              py::arg("values") = std::nullopt, py::arg("kernel") = NBKD_KERNEL_CUBIC,
              py::arg("count") = false)
+        .def("ball_profile", &PyKDTree::ball_profile, py::arg("points"), py::arg("radii"),
+             py::arg("values") = std::nullopt, py::arg("scale") = std::nullopt)
         .def("gravity", &PyKDTree::gravity, py::arg("points"), py::arg("mass") = std::nullopt,
              py::arg("theta") = 0.5f, py::arg("eps") = 0.0f, py::arg("potential") = true,
              py::arg("acceleration") = true)

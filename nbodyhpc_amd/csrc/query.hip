@@ -1921,6 +1921,91 @@ nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const floa
     return NBKD_OK;
 }
 
+// the per-bin sums of m device queries with device scales (or nullptr) into
+// the device array out_sum (m, nr, nv); vt = the values in tree order
+static nbkd_status profile_common(const Tree &t, Workspace &ws, const float *q, const float *scale,
+                                  uint64_t m, const ProfRadii &R, int nr, const float *vt, int nv,
+                                  float *out_sum, uint32_t flags, hipStream_t s) {
+    if (m == 0) return NBKD_OK;
+    const uint32_t mm = (uint32_t)m;
+    uint32_t *ord = nullptr;
+    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
+                                                : sort_queries(t, ws, q, mm, ord, s);
+    if (rc) return rc;
+    // periodic queries outside [0, L]^3: listed (the length stays in device
+    // memory), every point tested for them
+    uint32_t *list = nullptr;
+    if (t.periodic) {
+        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
+        if (!list) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
+        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(q, mm, t.box, list, list + mm);
+    }
+    TimedScope ts("ball_profile", s);
+    launch_ball_profile(t, q, scale, ord, mm, R, nr, vt, nv, out_sum, s);
+    if (list)
+        launch_ball_profile_outside_dev(t, q, scale, list, list + mm, R, nr, vt, nv, out_sum, s);
+    NBKD_HIP(hipGetLastError());
+    return NBKD_OK;
+}
+
+nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const float *scale,
+                               const float *radii, int nr, const float *values, int nv,
+                               float *out_sum, uint32_t flags, hipStream_t s) {
+    // the radii travel to the kernels by value (no host-to-device copy whose
+    // source could go away)
+    ProfRadii R;
+    for (int j = 0; j < NBKD_MAX_RADII; ++j) R.r[j] = radii[std::min(j, nr - 1)];
+    Workspace &ws = acquire_ws(t);
+    WsCall call(ws, s, std::adopt_lock);
+    NBKD_HIP(call.err);
+    const bool in_dev = (flags & NBKD_INPUT_DEVICE) != 0;
+    // the values once per call: uploaded when they are host memory, then
+    // gathered into tree order (vt[p] = values[row(p)], 1 without values)
+    const float *dvals = values;
+    if (values && !in_dev) {
+        const size_t vb = (size_t)t.n * (size_t)nv * 4;
+        float *up = (float *)ws.get(WS_VALS, vb, s);
+        if (!up) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemcpyAsync(up, values, vb, hipMemcpyHostToDevice, s));
+        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
+        dvals = up;
+    }
+    float *vt = (float *)ws.get(WS_VT, (size_t)t.n8 * (size_t)nv * 4, s);
+    if (!vt) return NBKD_ENOMEM;
+    {
+        TimedScope ts("ball_profile_gather", s);
+        launch_ball_sum_gather(t, dvals, nv, vt, s);
+        NBKD_HIP(hipGetLastError());
+    }
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    if ((flags & dev_io) == dev_io)
+        return profile_common(t, ws, q, scale, m, R, nr, vt, nv, out_sum, flags, s);
+    // host arrays stream in batches; each batch's slice of scale follows its
+    // queries (the pipeline hands over the batch, not its offset: b0 runs along)
+    const size_t ob[1] = {(size_t)nr * (size_t)nv * 4};
+    void *const outs[1] = {out_sum};
+    uint64_t b0 = 0;
+    const nbkd_status rc = host_pipeline(
+        ws, q, m, flags, 1, ob, outs, 44,
+        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
+            const float *dsc = scale ? scale + b0 : nullptr;
+            if (scale && !in_dev) {
+                float *hb = (float *)ws.get(WS_HRAD, (size_t)nb * 4, st);
+                if (!hb) return NBKD_ENOMEM;
+                NBKD_HIP(hipMemcpyAsync(hb, scale + b0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+                dsc = hb;
+            }
+            b0 += nb;
+            return profile_common(t, ws, dq, dsc, nb, R, nr, vt, nv, (float *)o[0], flags | dev_io,
+                                  st);
+        }, s);
+    if (rc) return rc;
+    // the caller's scale (pageable memory) has been read when the call returns
+    if (scale && !in_dev) NBKD_HIP(hipStreamSynchronize(s));
+    return NBKD_OK;
+}
+
 // the potentials and accelerations of m device queries into device outputs
 // (either may be nullptr); rec = the node moments, mt = the masses in tree order
 static nbkd_status gravity_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,

@@ -14,7 +14,9 @@ groups of the tree's points), ``fof_catalog`` (members, mass, centre, extent
 and value moments per group, reduced on the GPU), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
 ``interpolate`` (kernel-weighted sums over each query's own ball: the gather
-form of SPH), ``gravity`` / ``potential`` (Barnes-Hut potentials and
+form of SPH), ``profile`` / ``so_mass`` (weighted radial profiles in one tree
+walk, spherical-overdensity masses and radii read off them),
+``gravity`` / ``potential`` (Barnes-Hut potentials and
 accelerations from the tree's points as masses), ``group_potential`` /
 ``unbind`` (each group member's potential from its own group, the most-bound
 member, iterative unbinding), a ``device`` keyword, and
@@ -49,6 +51,7 @@ __all__ = ["KDTree", "cKDTree", "device_count"]
 _KERNELS = {"tophat": (0, 3.0 / (4.0 * math.pi)), "cubic": (1, 8.0 / math.pi),
             "wendland": (2, 21.0 / (2.0 * math.pi))}
 _MAX_VALUES = 4  # NBKD_MAX_VALUES
+_MAX_RADII = 32  # NBKD_MAX_RADII
 
 
 def _flatten(points):
@@ -57,6 +60,14 @@ def _flatten(points):
         shape = points.shape
         return points.reshape((-1, shape[-1])), shape
     return points, None
+
+
+def _geometric(lo, hi, n):
+    """n float32 edges from lo to hi in equal ratios, ascending (the two ends
+    exact: the float32 values of lo and hi)"""
+    g = np.exp(np.linspace(math.log(lo), math.log(hi), n)).astype(np.float32)
+    g[0], g[-1] = np.float32(lo), np.float32(hi)
+    return np.maximum.accumulate(g)
 
 
 class KDTree(cKDTree):
@@ -408,6 +419,192 @@ class KDTree(cKDTree):
         with np.errstate(divide="ignore", invalid="ignore"):
             out = s[..., :-1] / s[..., -1:]
         return out[..., 0] if f.ndim == 1 else out
+
+    # ---------------------------------------------------------------- radial profiles
+    def _profile_args(self, points, radii, values, scale):
+        """Checked arguments of a profile: (flat float32 points, output shape,
+        float32 radii (nr,), float32 values (N, nv) or None, whether values was
+        1-D or absent, float32 scale (M,) or None).  Runs before any device
+        call."""
+        r = np.asarray(radii, dtype=np.float32)
+        if r.ndim != 1:
+            raise ValueError("radii must be a 1-D array")
+        if r.size == 0:
+            raise ValueError("radii is empty: at least one radius is needed")
+        if r.size > _MAX_RADII:
+            raise ValueError(f"radii holds {r.size} radii: at most {_MAX_RADII} per call")
+        if not np.all(np.isfinite(r)) or np.any(r < 0):
+            raise ValueError("every radius must be finite and >= 0")
+        if np.any(r[1:] < r[:-1]):
+            raise ValueError("radii must be ascending (non-decreasing)")
+        points, shape = _flatten(points)
+        m = np.asarray(points).shape[0]
+        out_shape = tuple(shape[:-1]) if shape is not None else (m,)
+        sc = None
+        if scale is not None:
+            sc = np.asarray(scale, dtype=np.float64)
+            if not np.all(np.isfinite(sc)) or np.any(sc < 0):
+                raise ValueError("every scale must be finite and >= 0")
+            try:
+                sc = np.broadcast_to(sc, out_shape).reshape(-1)
+            except ValueError:
+                raise ValueError(f"scale of shape {np.shape(scale)} does not broadcast to the "
+                                 f"queries {out_shape}") from None
+            sc = np.ascontiguousarray(sc, dtype=np.float32)
+        vals, flat = None, True
+        if values is not None:
+            vals = np.asarray(values, dtype=np.float32)
+            if vals.ndim not in (1, 2) or vals.shape[0] != self._n_input:
+                raise ValueError(f"values must be (N,) or (N, nv) with N = {self._n_input} "
+                                 f"the tree's point count, got {vals.shape}")
+            flat = vals.ndim == 1
+            if not flat and not 1 <= vals.shape[1] <= _MAX_VALUES:
+                raise ValueError(f"values holds {vals.shape[1]} channels: 1 to {_MAX_VALUES} "
+                                 "per call")
+            vals = np.ascontiguousarray(vals.reshape(self._n_input, -1))
+        return points, out_shape, np.ascontiguousarray(r), vals, flat, sc
+
+    def profile(self, points: np.ndarray, radii, values=None, scale=None,
+                cumulative: bool = False):
+        """Weighted radial profiles around each query in one tree walk: the
+        sum of ``values`` over the tree points in each of the nr shells.
+
+        radii : 1-D ascending array of up to 32 shell edges (each finite and
+            >= 0; equal neighbours give an empty bin).
+        scale : None, or a scalar or array broadcast to the queries, finite and
+            >= 0: query i's edges are ``radii[k] * scale[i]`` (formed in
+            float32), so profiles come in units of each halo's own radius.
+        values : None (weight 1: counts), (N,) or (N, nv <= 4), indexed like the
+            tree's input points.
+
+        A point falls into bin b = the number of edges k with
+        ``not d2 <= fl(e_k * e_k)`` in float32 (the ``query_ball`` predicate):
+        bin 0 is the ball of the first edge, bin k the shell (e_{k-1}, e_k],
+        points beyond the last edge are dropped.  Returns the raw per-bin sums,
+        float32, shape points.shape[:-1] + (nr,) (+ (nv,) for 2-D values); with
+        cumulative=True their float64 running sum over the bins, the enclosed
+        sums M(<= e_k).  The device sums in float32, one accumulator per (query,
+        bin, channel) in a fixed order: identical calls give identical arrays.
+
+        After ``fof_catalog`` / ``group_potential`` the centres are the
+        catalogue's ``center`` rows or the most-bound members
+        (``points()[most_bound]``), and ``scale`` a radius per halo (for
+        instance ``so_mass(...)["radius"]``) for stacked profiles.
+        """
+        points, out_shape, r, vals, flat, sc = self._profile_args(points, radii, values, scale)
+        sums = super().ball_profile(points, r, vals, sc)
+        sums = sums.reshape(out_shape + ((r.size,) if flat else (r.size, sums.shape[2])))
+        if cumulative:
+            return np.cumsum(sums.astype(np.float64), axis=len(out_shape))
+        return sums
+
+    def so_mass(self, centres: np.ndarray, overdensity, r_max: float, mass=None,
+                r_min: Optional[float] = None, nbins: int = 32, refine: int = 1):
+        """Spherical-overdensity masses and radii (M200c / R200c and the like)
+        around each centre, from ``profile``.
+
+        overdensity : the threshold mean density (mass per volume in the
+            tree's units, for instance 200 times the critical density), a
+            scalar or one value per centre.
+        r_max, r_min : the search range; r_min defaults to r_max / 1000.
+        mass : (N,) particle masses or None (unit masses).
+        nbins : edges per pass (2 to 32); refine : further passes.
+
+        The first pass takes ``nbins`` geometric edges e_k from r_min to r_max,
+        M_k = the float64 running sum of the bins and the enclosed mean density
+        rho_k = M_k / (4/3 pi e_k^3) (float64, from the float32 edges).  k* is
+        the smallest k with rho_k < overdensity: status 1 if k* == 0 (already
+        below at r_min), status 2 if there is none (no crossing within r_max),
+        otherwise the crossing lies in the bracket [e_{k*-1}, e_{k*}].  Each
+        further pass profiles the bracket alone, in units of its lower edge
+        (``scale`` = r_lo: bin 0 recounts M(<= r_lo)), with ``nbins`` geometric
+        edges from 1 to the previous edge ratio times (1 + 2^-20), and narrows
+        the bracket the same way; a pass that does not bracket a crossing
+        leaves the earlier bracket.
+
+        Returns a dict of arrays over the centres: ``radius`` (the log-log
+        interpolation of the mean density inside the bracket), ``mass`` =
+        overdensity * 4/3 pi radius^3, the bracket ``r_lo``, ``r_hi`` (float32
+        edges) with the enclosed masses ``m_lo``, ``m_hi`` (float64), and
+        ``status`` (0: found).  radius and mass are NaN where status != 0.
+        Works on periodic and non-periodic trees (keep r_max below half the
+        box).
+
+        After ``fof_catalog`` the centres are ``cat["center"]``; after
+        ``group_potential`` / ``unbind`` the most-bound members,
+        ``points()[most_bound]``.
+        """
+        nbins, refine = int(nbins), int(refine)
+        if not 2 <= nbins <= _MAX_RADII:
+            raise ValueError(f"nbins must be in [2, {_MAX_RADII}], got {nbins}")
+        if refine < 0:
+            raise ValueError(f"refine must be >= 0, got {refine}")
+        r_max = float(r_max)
+        r_min = r_max / 1000.0 if r_min is None else float(r_min)
+        if not (math.isfinite(r_max) and math.isfinite(r_min) and 0.0 < r_min < r_max):
+            raise ValueError("r_min and r_max must be finite with 0 < r_min < r_max")
+        centres, shape = _flatten(centres)
+        centres = np.asarray(centres)
+        if centres.ndim != 2 or centres.shape[1] != 3:
+            raise ValueError("centres must be an array of shape (..., 3)")
+        m = centres.shape[0]
+        out_shape = tuple(shape[:-1]) if shape is not None else (m,)
+        delta = np.asarray(overdensity, dtype=np.float64)
+        if not np.all(np.isfinite(delta)) or np.any(delta <= 0):
+            raise ValueError("overdensity must be finite and > 0")
+        try:
+            delta = np.broadcast_to(delta, out_shape).reshape(-1)
+        except ValueError:
+            raise ValueError(f"overdensity of shape {np.shape(overdensity)} does not broadcast "
+                             f"to the centres {out_shape}") from None
+        if mass is not None and (np.ndim(mass) != 1 or np.shape(mass)[0] != self._n_input):
+            raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point count")
+        vol = 4.0 / 3.0 * math.pi
+
+        def crossing(edges, cum, thresh):
+            """per row the smallest k with rho_k < thresh, or -1"""
+            with np.errstate(divide="ignore", invalid="ignore"):
+                rho = cum / (vol * edges.astype(np.float64) ** 3)
+            below = rho < thresh[:, None]
+            return np.where(below.any(axis=1), below.argmax(axis=1), -1)
+
+        # pass 1: shared edges
+        grid = _geometric(r_min, r_max, nbins)
+        cum = np.asarray(self.profile(centres, grid, mass, None, True), np.float64).reshape(m, nbins)
+        k = crossing(np.broadcast_to(grid, (m, nbins)), cum, delta)
+        status = np.where(k == 0, 1, np.where(k < 0, 2, 0)).astype(np.int32)
+        good = np.flatnonzero(status == 0)
+        r_lo = np.full(m, np.nan, np.float32)
+        r_hi = np.full(m, np.nan, np.float32)
+        m_lo = np.full(m, np.nan)
+        m_hi = np.full(m, np.nan)
+        r_lo[good], r_hi[good] = grid[k[good] - 1], grid[k[good]]
+        m_lo[good], m_hi[good] = cum[good, k[good] - 1], cum[good, k[good]]
+        ratio = float(np.max(grid[1:].astype(np.float64) / grid[:-1].astype(np.float64)))
+        for _ in range(refine):
+            if good.size == 0:
+                break
+            grid = _geometric(1.0, ratio * (1.0 + 2.0 ** -20), nbins)
+            s = r_lo[good]
+            cum = np.asarray(self.profile(centres[good], grid, mass, s, True),
+                             np.float64).reshape(good.size, nbins)
+            edges = grid[None, :] * s[:, None]  # float32 products, the device's edges
+            k = crossing(edges, cum, delta[good])
+            hit = np.flatnonzero(k > 0)
+            g = good[hit]
+            r_lo[g], r_hi[g] = edges[hit, k[hit] - 1], edges[hit, k[hit]]
+            m_lo[g], m_hi[g] = cum[hit, k[hit] - 1], cum[hit, k[hit]]
+            ratio = float(np.max(grid[1:].astype(np.float64) / grid[:-1].astype(np.float64)))
+        # log-log interpolation of the mean density inside the bracket
+        lo64, hi64 = r_lo.astype(np.float64), r_hi.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rho_lo, rho_hi = m_lo / (vol * lo64 ** 3), m_hi / (vol * hi64 ** 3)
+            f = np.log(rho_lo / delta) / np.log(rho_lo / rho_hi)
+            radius = np.clip(lo64 * (hi64 / lo64) ** f, lo64, hi64)
+        radius = np.where(status == 0, radius, np.nan)
+        res = {"radius": radius, "mass": delta * vol * radius ** 3, "r_lo": r_lo, "r_hi": r_hi,
+               "m_lo": m_lo, "m_hi": m_hi, "status": status}
+        return {name: a.reshape(out_shape) for name, a in res.items()}
 
     # ---------------------------------------------------------------- gravity
     def gravity(self, points: Optional[np.ndarray] = None, mass=None, softening: float = 0.0,
