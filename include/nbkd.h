@@ -314,7 +314,7 @@ nbkd_status nbkd_query_ball_profile(const nbkd_tree *tree, const float *q, uint6
  *   out_phi  (m,) float32 or NULL;  out_acc (m, 3) row-major float32 or NULL; at
  *            least one; both host, or both device with NBKD_OUTPUT_DEVICE
  * Non-periodic trees only: a periodic tree is NBKD_EINVAL (Ewald sums are not
- * provided).
+ * provided).  nbkd_gravity_ewald below is the call for a periodic tree.
  * Everything below is float32 without fused multiply-adds unless float64 is
  * stated.
  * Node moments.  Each node with at least one real point has moments; padding
@@ -362,6 +362,100 @@ nbkd_status nbkd_gravity(const nbkd_tree *tree, const float *q, uint64_t m,
                          const float *mass, float theta, float eps,
                          float *out_phi, float *out_acc,
                          uint32_t flags, void *stream);
+
+/*
+ * NEW (no reference counterpart): nbkd_gravity on a periodic tree: Barnes-Hut
+ * potentials and accelerations of the tree's points and all their periodic
+ * images (box size L), G = 1.  Arguments, sides, flags and streaming are those
+ * of nbkd_gravity; here a non-periodic tree is the one rejected.
+ * Definition.  In units of the box, with x in [-1/2, 1/2]^3, the periodic
+ * potential of a unit mass at offset x is -psi(x), with zero mean over the box:
+ *   psi(x)       = sum_n erfc(a|x-n|)/|x-n|
+ *                  + (1/pi) sum_{h != 0} exp(-pi^2 |h|^2/a^2)/|h|^2 * cos(2 pi h.x)
+ *                  - pi/a^2
+ *   -grad psi(x) = sum_n (x-n)/r^3 * [erfc(a r) + (2 a r/sqrt(pi)) exp(-a^2 r^2)]
+ *                  + 2 sum_{h != 0} (h/|h|^2) exp(-pi^2 |h|^2/a^2) sin(2 pi h.x)
+ * (r = |x-n|; n and h run over the integer triples; the value does not depend
+ * on the splitting parameter a).  The corrections to the nearest image's
+ * Newtonian term are
+ *   C_phi(x) = psi(x) - 1/|x|,      C_a(x) = -grad psi(x) - x/|x|^3,
+ * with C_phi(0) = -2.8372975 (the limit) and C_a(0) = 0.  C_phi is even in
+ * every axis; component a of C_a is odd in axis a and even in the other two.
+ * Table.  NBKD_EWALD_N = 64 intervals over [0, 1/2] per axis: 65^3 nodes
+ * x = (i, j, k)/128 of 4 float32 each (C_phi, C_ax, C_ay, C_az), 4.39 MB, the
+ * node index of x slowest.  It is computed on the host in float64 once per
+ * process (first use; host threads, at most 16), in units of the box, so one
+ * table serves every L, and uploaded once per device.  Each stored value is
+ * within 2e-9 absolute of the converged sum before it is rounded to float32;
+ * node (0, 0, 0) holds (-2.8372975f, 0, 0, 0), and component a is 0 on the
+ * plane x_a = 0.  nbkd_ewald_table copies it out.
+ * Everything below is float32 without fused multiply-adds unless float64 is
+ * stated.  Per call, on the host: iL = 1.0f/L, sc = 128.0f*iL, iL2 = iL*iL.
+ * Offset.  Per axis the raw d = p - q is replaced by the nearest image: the
+ * one of d, fl(d - L), fl(d + L) with the smallest magnitude, ties to the
+ * earlier in that order (nbkd_group_catalog's rule).  Then
+ * d2 = (d.x*d.x + d.y*d.y) + d.z*d.z.
+ * Node moments, the opening test and the order of the terms are exactly
+ * nbkd_gravity's, with d the wrapped offset: moments in float64 per node (they
+ * do not depend on periodicity); a node is accepted iff theta*theta > 0 and
+ * s2 <= (theta*theta)*d2 with d the wrapped offset to c; the walk is
+ * depth-first and left-first, an accepted node adds its monopole (M, c), a
+ * leaf that is not accepted adds its real points by ascending tree position.
+ * With theta < 1 an accepted node has s < |d| <= (sqrt(3)/2) L, so no image of
+ * the query lies inside its box.
+ * One term with mass mu at wrapped offset d: d2 == 0 adds nothing (the query
+ * itself, a coincident point, for every eps).  The constant -2.8372975*m/L
+ * that a particle's own images add to its potential is thereby left out (it
+ * exerts no force); a caller who wants it adds it.  Otherwise first the
+ * Newtonian part exactly as in nbkd_gravity (the Plummer softening eps acts on
+ * this part only):
+ *   r2 = d2 + eps*eps;  inv = 1.0f / sqrtf(r2);
+ *   phi -= mu*inv;  w = mu*((inv*inv)*inv);
+ *   acc.x += w*d.x;  acc.y += w*d.y;  acc.z += w*d.z;
+ * then the correction, per axis a:
+ *   t_a = fabsf(d_a)*sc;  i_a = min((int)t_a, 63);  f_a = t_a - (float)i_a;
+ * each of the four channels is interpolated trilinearly between the eight
+ * nodes (i_x + 0|1, i_y + 0|1, i_z + 0|1), every step as a + f*(b - a): along
+ * x (four values), then along y (two), then along z; component a of C_a is
+ * negated when d_a < 0; then
+ *   phi = phi - (mu*iL)*C_phi;
+ *   acc.x = acc.x + (mu*iL2)*C_ax;  likewise y and z.
+ * phi and acc start at 0.  Over 20 000 sampled offsets the interpolation errs
+ * by up to 1.2e-4/L per unit mass in the potential and 5.6e-4/L^2 in an
+ * acceleration component (the tests hold it below 1.5e-4 and 7e-4).
+ * Outside queries.  A query with a coordinate outside [0, L] or NaN takes no
+ * part in the walk: its potential and its three acceleration components are
+ * quiet NaNs.  A caller wraps such points into the box first.
+ * Deterministic: each query is summed by one lane into one float32 register per
+ * component, in exactly this order.  The order depends on the tree, the query,
+ * theta and eps only: not on the other queries of the call, the path (the
+ * tree's build array as device queries takes the self-order path, other
+ * queries are bucketed and sorted), the host batch size, the grid or timing.
+ * There are no floating-point atomics.  Two calls give arrays equal under ==,
+ * and so do the self-order path, the bucketed path and every host batch size.
+ * A call with one output gives that output exactly as the call with both.
+ * NBKD_EINVAL before any device call, outputs untouched: NULL tree or q; both
+ * outputs NULL; theta NaN, negative or >= 1; eps NaN, negative or infinite;
+ * m >= 2^32; a tree that is not periodic (the message names nbkd_gravity).
+ * m == 0 is NBKD_OK.  With device inputs and outputs the call returns once the
+ * work is enqueued; host arrays stream in batches; mass is uploaded once per
+ * call, all as in nbkd_gravity.  Scratch: nbkd_gravity's; the table lives per
+ * device, outside the workspaces, for the life of the process.
+ */
+#define NBKD_EWALD_N 64
+nbkd_status nbkd_gravity_ewald(const nbkd_tree *tree, const float *q, uint64_t m,
+                               const float *mass, float theta, float eps,
+                               float *out_phi, float *out_acc,
+                               uint32_t flags, void *stream);
+
+/*
+ * The correction table of nbkd_gravity_ewald, copied to host memory:
+ * (NBKD_EWALD_N + 1)^3 * 4 floats, [i][j][k][C_phi, C_ax, C_ay, C_az] for the
+ * offset (i, j, k)/(2*NBKD_EWALD_N) in units of the box.  Needs no device (the
+ * first call of a process computes the table).  NBKD_EINVAL if out is NULL or
+ * capacity (in floats) is too small.
+ */
+nbkd_status nbkd_ewald_table(float *out, uint64_t capacity);
 
 /*
  * NEW (no reference counterpart): the group catalogue of a labelling of the

@@ -25,6 +25,7 @@ NBKD_SORTED = 0x10
 KERNEL_TOPHAT, KERNEL_CUBIC, KERNEL_WENDLAND = 0, 1, 2
 NBKD_MAX_VALUES = 4
 NBKD_MAX_RADII = 32
+NBKD_EWALD_N = 64
 
 NODE_DTYPE = np.dtype([("dim", "<i4"), ("split", "<f4"), ("left", "<u4"), ("right", "<u4")])
 
@@ -56,6 +57,9 @@ _PROTOS = {
                                        _c_p]),
     "nbkd_gravity": (_i32, [_c_p, _c_p, _u64, _c_p, ctypes.c_float, ctypes.c_float, _c_p, _c_p,
                             _u32, _c_p]),
+    "nbkd_gravity_ewald": (_i32, [_c_p, _c_p, _u64, _c_p, ctypes.c_float, ctypes.c_float, _c_p,
+                                  _c_p, _u32, _c_p]),
+    "nbkd_ewald_table": (_i32, [_c_p, _u64]),
     "nbkd_query_ball_csr": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _c_p, _u64, _u32,
                                    _c_p]),
     "nbkd_fof": (_i32, [_c_p, ctypes.c_float, _c_p, _c_p, ctypes.POINTER(_u64), _u32, _c_p]),
@@ -366,6 +370,33 @@ class Tree:
                                   phi_ptr, acc_ptr, NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE,
                                   stream))
 
+    def gravity_ewald(self, q, mass=None, theta=0.5, eps=0.0, phi=True, acc=True):
+        """nbkd_gravity_ewald of host arrays on a periodic tree, G = 1: (phi
+        (m,) float32 or None, acc (m, 3) float32 or None), the arguments of
+        gravity.  A query outside [0, L]^3 gets NaNs."""
+        q = _host_f32(q).reshape(-1, 3)
+        m = q.shape[0]
+        w = None
+        if mass is not None:
+            w = _host_f32(mass)
+            if w.shape != (self.npoints,):
+                raise ValueError("mass must be (n,) with n the tree's point count")
+        p = np.empty(m, np.float32) if phi else None
+        a = np.empty((m, 3), np.float32) if acc else None
+        _check(lib().nbkd_gravity_ewald(self.h, q.ctypes.data, m,
+                                        None if w is None else w.ctypes.data, float(theta),
+                                        float(eps), p.ctypes.data if phi else None,
+                                        a.ctypes.data if acc else None, 0, None))
+        return p, a
+
+    def gravity_ewald_device(self, q_ptr, m, mass_ptr, theta, eps, phi_ptr, acc_ptr=None,
+                             stream=None):
+        """Device queries, masses ((n,) or None) and outputs ((m,) float32
+        potentials and / or (m, 3) float32 accelerations); returns once enqueued."""
+        _check(lib().nbkd_gravity_ewald(self.h, q_ptr, int(m), mass_ptr, float(theta), float(eps),
+                                        phi_ptr, acc_ptr, NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE,
+                                        stream))
+
     def fof(self, b, sizes=True):
         """nbkd_fof into host arrays: (labels (n,) uint32 = the smallest input
         row of each point's group, sizes (n,) uint32 or None, ngroups)."""
@@ -535,6 +566,16 @@ def deposit_device(xyz_ptr, weight_ptr, radius_ptr, n, grid, ppu, out_ptr,
     _check(lib().nbkd_deposit(xyz_ptr, weight_ptr, radius_ptr, int(n), gx, gy, nz, float(ppu),
                               per.ctypes.data, int(subsample), int(mode), x0, wx, out_ptr,
                               int(device), flags, stream))
+
+
+def ewald_table():
+    """nbkd_ewald_table: the correction table of nbkd_gravity_ewald, float32
+    (65, 65, 65, 4): [i, j, k] = (C_phi, C_ax, C_ay, C_az) at the offset
+    (i, j, k) / 128 in units of the box.  Needs no device."""
+    nn = NBKD_EWALD_N + 1
+    out = np.empty((nn, nn, nn, 4), np.float32)
+    _check(lib().nbkd_ewald_table(out.ctypes.data, out.size))
+    return out
 
 
 def set_tuning(name, value):

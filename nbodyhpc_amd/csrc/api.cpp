@@ -404,11 +404,15 @@ CopyPool &copy_pool() {
 }
 } // namespace
 
-void host_copy(void *dst, const void *src, size_t bytes) {
-    if (bytes == 0) return;
+int host_workers() {
     static const int cpus = usable_cpus();
     const double tw = tuning(TUNE_HOST_THREADS);
-    const int workers = tw >= 1.0 ? (int)std::min(tw, 256.0) : std::min(cpus, 16);
+    return tw >= 1.0 ? (int)std::min(tw, 256.0) : std::min(cpus, 16);
+}
+
+void host_copy(void *dst, const void *src, size_t bytes) {
+    if (bytes == 0) return;
+    const int workers = host_workers();
     if (workers <= 1 || bytes < (16u << 20)) {
         std::memcpy(dst, src, bytes);
         return;
@@ -760,6 +764,57 @@ nbkd_status nbkd_gravity(const nbkd_tree *tree, const float *q, uint64_t m, cons
     DeviceGuard g(tree->t.device);
     return query_gravity(tree->t, q, m, mass, theta, eps, out_phi, out_acc, flags,
                          (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
+nbkd_status nbkd_gravity_ewald(const nbkd_tree *tree, const float *q, uint64_t m,
+                               const float *mass, float theta, float eps, float *out_phi,
+                               float *out_acc, uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q) {
+        set_error("nbkd_gravity_ewald: NULL argument (tree or q)");
+        return NBKD_EINVAL;
+    }
+    if (!out_phi && !out_acc) {
+        set_error("nbkd_gravity_ewald: out_phi and out_acc are both NULL");
+        return NBKD_EINVAL;
+    }
+    if (!(theta >= 0.0f) || !(theta < 1.0f)) {
+        set_error("nbkd_gravity_ewald: the opening angle theta must be in [0, 1)");
+        return NBKD_EINVAL;
+    }
+    if (!(eps >= 0.0f) || !(eps <= FLT_MAX)) {
+        set_error("nbkd_gravity_ewald: the softening eps is NaN, infinite or negative");
+        return NBKD_EINVAL;
+    }
+    if (m >= (1ull << 32)) {
+        set_error("more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) return NBKD_OK;
+    if (!tree->t.periodic) {
+        set_error("nbkd_gravity_ewald: the tree is not periodic; nbkd_gravity sums a "
+                  "non-periodic tree");
+        return NBKD_EINVAL;
+    }
+    DeviceGuard g(tree->t.device);
+    return query_gravity_ewald(tree->t, q, m, mass, theta, eps, out_phi, out_acc, flags,
+                               (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
+nbkd_status nbkd_ewald_table(float *out, uint64_t capacity) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    const uint64_t need = (uint64_t)(NBKD_EWALD_N + 1) * (NBKD_EWALD_N + 1) * (NBKD_EWALD_N + 1) * 4;
+    if (!out || capacity < need) {
+        set_error("nbkd_ewald_table: out is NULL or holds fewer than " + std::to_string(need) +
+                  " floats");
+        return NBKD_EINVAL;
+    }
+    std::memcpy(out, ewald_table_host(), (size_t)need * 4);
+    return NBKD_OK;
     NBKD_GUARD_END
 }
 

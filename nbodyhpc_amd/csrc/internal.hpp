@@ -241,6 +241,9 @@ enum TuneId {
 // pipeline's pinned staging <-> the caller's arrays; small copies stay on the
 // calling thread
 void host_copy(void *dst, const void *src, size_t bytes);
+// the number of host threads such work is split over ("host_threads", else the
+// usable CPUs, at most 16)
+int host_workers();
 // the calling thread's interrupt check (nbkd_set_interrupt): true = abandon
 // the call (host-buffer calls check it between batches)
 bool interrupted();
@@ -463,6 +466,16 @@ void launch_gravity_walk(const Tree &t, const void *rec, const float *q, const u
                          uint32_t m, const float *mt, float th2, float eps2, float *out_phi,
                          float *out_acc, hipStream_t s);
 
+// gravity_ewald.hip: the same on a periodic tree (nbkd_gravity_ewald).  The
+// correction table ((NBKD_EWALD_N + 1)^3 nodes of 4 floats, units of the box)
+// is computed once per process on the host and uploaded once per device; the
+// walk takes the device copy beside launch_gravity_moments' records
+const float *ewald_table_host();
+nbkd_status ewald_table_device(int device, const void **out);
+void launch_gravity_ewald_walk(const Tree &t, const void *rec, const void *table, const float *q,
+                               const uint32_t *order, uint32_t m, const float *mt, float th2,
+                               float eps2, float *out_phi, float *out_acc, hipStream_t s);
+
 // per-row sort of a CSR batch (row offsets `off`, nrows + 1 entries, device):
 // rows of up to csr_sort_row_cap() ids in place; longer rows are appended to
 // long_rows (count in *nlong, zeroed by the caller) for the caller to sort
@@ -502,6 +515,10 @@ nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const 
 nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float *mass,
                           float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
                           hipStream_t s);
+// the same on a periodic tree, with the Ewald correction (nbkd_gravity_ewald)
+nbkd_status query_gravity_ewald(const Tree &t, const float *q, uint64_t m, const float *mass,
+                                float theta, float eps, float *out_phi, float *out_acc,
+                                uint32_t flags, hipStream_t s);
 
 // fof.hip: friends-of-friends groups of the tree's own points (b finite and
 // >= 0, out_label != nullptr: checked by the caller, api.cpp)

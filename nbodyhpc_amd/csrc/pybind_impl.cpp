@@ -7,7 +7,7 @@
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
 // (query_ball_count / query_ball_csr / query_ball_hist), kernel-weighted sums
-// (ball_sum), radial profiles (ball_profile), gravity, fof_labels, group_moments, group_potential and export()
+// (ball_sum), radial profiles (ball_profile), gravity, gravity_ewald, fof_labels, group_moments, group_potential and export()
 // for parity tests.
 // `max_threads` and `workers` are accepted and ignored: the build and the
 // queries run on the GPU (the reference ignores max_threads too,
@@ -295,6 +295,18 @@ class PyKDTree {
     // mass: None (mass 1) or an (N,) array by input row.
     py::tuple gravity(farray points, std::optional<farray> mass, float theta, float eps,
                       bool potential, bool acceleration) {
+        return gravity_call(false, points, mass, theta, eps, potential, acceleration);
+    }
+
+    // the same on a periodic tree, with the Ewald correction (nbkd_gravity_ewald);
+    // a query outside [0, L]^3 gets NaNs
+    py::tuple gravity_ewald(farray points, std::optional<farray> mass, float theta, float eps,
+                            bool potential, bool acceleration) {
+        return gravity_call(true, points, mass, theta, eps, potential, acceleration);
+    }
+
+    py::tuple gravity_call(bool ewald, farray points, std::optional<farray> mass, float theta,
+                           float eps, bool potential, bool acceleration) {
         check_shape(points);
         const py::ssize_t m = points.shape(0);
         const float *w = nullptr;
@@ -325,7 +337,8 @@ class PyKDTree {
         Interruptible intr;
         {
             py::gil_scoped_release nogil;
-            st = nbkd_gravity(h_, q, (uint64_t)m, w, theta, eps, pp, ap, 0u, nullptr);
+            st = ewald ? nbkd_gravity_ewald(h_, q, (uint64_t)m, w, theta, eps, pp, ap, 0u, nullptr)
+                       : nbkd_gravity(h_, q, (uint64_t)m, w, theta, eps, pp, ap, 0u, nullptr);
         }
         intr.finish(st);
         return py::make_tuple(phi, acc);
@@ -515,6 +528,9 @@ PYBIND11_MODULE(_impl, m) {
         .def("gravity", &PyKDTree::gravity, py::arg("points"), py::arg("mass") = std::nullopt,
              py::arg("theta") = 0.5f, py::arg("eps") = 0.0f, py::arg("potential") = true,
              py::arg("acceleration") = true)
+        .def("gravity_ewald", &PyKDTree::gravity_ewald, py::arg("points"),
+             py::arg("mass") = std::nullopt, py::arg("theta") = 0.5f, py::arg("eps") = 0.0f,
+             py::arg("potential") = true, py::arg("acceleration") = true)
         .def("fof_labels", &PyKDTree::fof_labels, py::arg("b"))
         .def("group_moments", &PyKDTree::group_moments, py::arg("labels"),
              py::arg("min_members") = 1, py::arg("weight") = std::nullopt,

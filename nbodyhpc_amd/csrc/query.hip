@@ -2007,25 +2007,34 @@ nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const 
 }
 
 // the potentials and accelerations of m device queries into device outputs
-// (either may be nullptr); rec = the node moments, mt = the masses in tree order
+// (either may be nullptr); rec = the node moments, mt = the masses in tree
+// order, table = the device Ewald table (periodic trees) or nullptr
 static nbkd_status gravity_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
-                                  const void *rec, const float *mt, float th2, float eps2,
-                                  float *out_phi, float *out_acc, uint32_t flags, hipStream_t s) {
+                                  const void *rec, const void *table, const float *mt, float th2,
+                                  float eps2, float *out_phi, float *out_acc, uint32_t flags,
+                                  hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
     uint32_t *ord = nullptr;
     nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
                                                 : sort_queries(t, ws, q, mm, ord, s);
     if (rc) return rc;
+    if (table) {
+        TimedScope ts("gravity_ewald_walk", s);
+        launch_gravity_ewald_walk(t, rec, table, q, ord, mm, mt, th2, eps2, out_phi, out_acc, s);
+        NBKD_HIP(hipGetLastError());
+        return NBKD_OK;
+    }
     TimedScope ts("gravity_walk", s);
     launch_gravity_walk(t, rec, q, ord, mm, mt, th2, eps2, out_phi, out_acc, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
 
-nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float *mass,
-                          float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
-                          hipStream_t s) {
+// nbkd_gravity (table == nullptr) and nbkd_gravity_ewald (the device table)
+static nbkd_status gravity_call(const Tree &t, const float *q, uint64_t m, const float *mass,
+                                float theta, float eps, const void *table, float *out_phi,
+                                float *out_acc, uint32_t flags, hipStream_t s) {
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
@@ -2067,7 +2076,7 @@ nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float
     const float th2 = theta * theta, eps2 = eps * eps;
     const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
     if ((flags & dev_io) == dev_io)
-        return gravity_common(t, ws, q, m, rec, mt, th2, eps2, out_phi, out_acc, flags, s);
+        return gravity_common(t, ws, q, m, rec, table, mt, th2, eps2, out_phi, out_acc, flags, s);
     size_t ob[2];
     void *outs[2];
     int nout = 0;
@@ -2084,10 +2093,27 @@ nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float
     return host_pipeline(
         ws, q, m, flags, nout, ob, outs, 40,
         [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
-            return gravity_common(t, ws, dq, nb, rec, mt, th2, eps2,
+            return gravity_common(t, ws, dq, nb, rec, table, mt, th2, eps2,
                                   iphi >= 0 ? (float *)o[iphi] : nullptr,
                                   iacc >= 0 ? (float *)o[iacc] : nullptr, flags | dev_io, st);
         }, s);
+}
+
+nbkd_status query_gravity(const Tree &t, const float *q, uint64_t m, const float *mass,
+                          float theta, float eps, float *out_phi, float *out_acc, uint32_t flags,
+                          hipStream_t s) {
+    return gravity_call(t, q, m, mass, theta, eps, nullptr, out_phi, out_acc, flags, s);
+}
+
+nbkd_status query_gravity_ewald(const Tree &t, const float *q, uint64_t m, const float *mass,
+                                float theta, float eps, float *out_phi, float *out_acc,
+                                uint32_t flags, hipStream_t s) {
+    // (before a workspace is taken: the first call of a process computes the
+    // table on the host, the first on a device uploads it)
+    const void *table = nullptr;
+    const nbkd_status rc = ewald_table_device(t.device, &table);
+    if (rc) return rc;
+    return gravity_call(t, q, m, mass, theta, eps, table, out_phi, out_acc, flags, s);
 }
 
 // the radius histogram of m device queries: rows into the device array

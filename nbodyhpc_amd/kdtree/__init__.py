@@ -17,7 +17,9 @@ neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
 form of SPH), ``profile`` / ``so_mass`` (weighted radial profiles in one tree
 walk, spherical-overdensity masses and radii read off them),
 ``gravity`` / ``potential`` (Barnes-Hut potentials and
-accelerations from the tree's points as masses), ``group_potential`` /
+accelerations from the tree's points as masses), ``gravity_ewald`` /
+``potential_ewald`` (the same on a periodic tree: an Ewald sum over all
+images), ``group_potential`` /
 ``unbind`` (each group member's potential from its own group, the most-bound
 member, iterative unbinding), a ``device`` keyword, and
 persistence: ``points()``, ``save`` / ``load`` (.npz,
@@ -607,6 +609,30 @@ class KDTree(cKDTree):
         return {name: a.reshape(out_shape) for name, a in res.items()}
 
     # ---------------------------------------------------------------- gravity
+    def _gravity_args(self, mass, softening, theta, potential, acceleration):
+        """Checked arguments of ``gravity`` / ``gravity_ewald``: (float32 masses
+        (N,) or None, theta, eps).  Runs before any device call."""
+        w = None
+        if mass is not None:
+            w = np.asarray(mass, dtype=np.float32)
+            if w.shape != (self._n_input,):
+                raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point "
+                                 f"count, got {w.shape}")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("every mass must be finite and >= 0")
+            w = np.ascontiguousarray(w)
+        th = float(theta)
+        if not 0.0 <= th < 1.0 or not np.float32(th) < np.float32(1.0):
+            raise ValueError(f"theta must be in [0, 1), got {theta!r}")
+        eps = float(softening)
+        with np.errstate(over="ignore"):
+            eps_ok = math.isfinite(eps) and eps >= 0.0 and bool(np.isfinite(np.float32(eps)))
+        if not eps_ok:
+            raise ValueError(f"softening must be finite and >= 0, got {softening!r}")
+        if not (potential or acceleration):
+            raise ValueError("at least one of potential and acceleration is needed")
+        return w, th, eps
+
     def gravity(self, points: Optional[np.ndarray] = None, mass=None, softening: float = 0.0,
                 theta: float = 0.5, G: float = 1.0, potential: bool = True,
                 acceleration: bool = True):
@@ -630,27 +656,9 @@ class KDTree(cKDTree):
         or ``acceleration=False`` is None.  The device sums in float32, one
         accumulator per query and component in an order fixed by the tree and
         the query: identical calls give identical arrays, whatever else is
-        asked in the same call.  Periodic trees are not supported (no Ewald
-        sum)."""
-        w = None
-        if mass is not None:
-            w = np.asarray(mass, dtype=np.float32)
-            if w.shape != (self._n_input,):
-                raise ValueError(f"mass must be (N,) with N = {self._n_input} the tree's point "
-                                 f"count, got {w.shape}")
-            if not np.all(np.isfinite(w)) or np.any(w < 0):
-                raise ValueError("every mass must be finite and >= 0")
-            w = np.ascontiguousarray(w)
-        th = float(theta)
-        if not 0.0 <= th < 1.0 or not np.float32(th) < np.float32(1.0):
-            raise ValueError(f"theta must be in [0, 1), got {theta!r}")
-        eps = float(softening)
-        with np.errstate(over="ignore"):
-            eps_ok = math.isfinite(eps) and eps >= 0.0 and bool(np.isfinite(np.float32(eps)))
-        if not eps_ok:
-            raise ValueError(f"softening must be finite and >= 0, got {softening!r}")
-        if not (potential or acceleration):
-            raise ValueError("at least one of potential and acceleration is needed")
+        asked in the same call.  Periodic trees are not supported here (no Ewald
+        sum): ``gravity_ewald`` is the call for them."""
+        w, th, eps = self._gravity_args(mass, softening, theta, potential, acceleration)
         if self.periodic:
             raise ValueError("gravity needs a non-periodic tree: Ewald sums are not provided")
         if points is None:
@@ -668,6 +676,50 @@ class KDTree(cKDTree):
                   theta: float = 0.5, G: float = 1.0):
         """The potential alone: ``gravity(..., acceleration=False)[0]``."""
         return self.gravity(points, mass, softening, theta, G, True, False)[0]
+
+    def gravity_ewald(self, points: Optional[np.ndarray] = None, mass=None,
+                      softening: float = 0.0, theta: float = 0.5, G: float = 1.0,
+                      potential: bool = True, acceleration: bool = True):
+        """``gravity`` on a periodic tree: the potential and acceleration from
+        the tree's points and all their periodic images (an Ewald sum, zero
+        mean potential over the box), by the same Barnes-Hut walk with every
+        offset taken to its nearest image and a tabulated correction added to
+        each term.
+
+        The arguments and results are those of ``gravity``.  Points outside
+        the box are wrapped into [0, L) in float64 first.  The softening acts
+        on the nearest image's Newtonian term only.  A point at the query's
+        own position adds nothing, so the constant ``-2.8372975 G m / L`` of a
+        particle's own images is not part of its potential.  The tabulated
+        correction is interpolated: per unit mass it errs by up to about
+        1.2e-4 / L in the potential and 5.6e-4 / L^2 in an acceleration
+        component.  A non-periodic tree raises ValueError (use ``gravity``)."""
+        w, th, eps = self._gravity_args(mass, softening, theta, potential, acceleration)
+        if not self.periodic:
+            raise ValueError("gravity_ewald needs a periodic tree: gravity sums a non-periodic "
+                             "one")
+        if points is None:
+            points = self.points()
+        points, shape = _flatten(points)
+        out_shape = tuple(shape[:-1]) if shape is not None else (np.asarray(points).shape[0],)
+        L = float(self.boxsize)
+        p64 = np.asarray(points, dtype=np.float64)
+        p64 = p64 - L * np.floor(p64 / L)
+        p32 = p64.astype(np.float32)
+        # (a value just below L can round up to L, which is the same place as 0)
+        p32[p32 >= np.float32(L)] = 0.0
+        phi, acc = super().gravity_ewald(np.ascontiguousarray(p32), w, th, eps, bool(potential),
+                                         bool(acceleration))
+        if phi is not None:
+            phi = (float(G) * phi.astype(np.float64)).reshape(out_shape)
+        if acc is not None:
+            acc = (float(G) * acc.astype(np.float64)).reshape(out_shape + (3,))
+        return phi, acc
+
+    def potential_ewald(self, points: Optional[np.ndarray] = None, mass=None,
+                        softening: float = 0.0, theta: float = 0.5, G: float = 1.0):
+        """The potential alone: ``gravity_ewald(..., acceleration=False)[0]``."""
+        return self.gravity_ewald(points, mass, softening, theta, G, True, False)[0]
 
     # ---------------------------------------------------------------- group potentials
     def _group_args(self, offsets, members, mass, softening, theta, max_direct):
