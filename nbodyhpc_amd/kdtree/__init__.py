@@ -227,8 +227,11 @@ class KDTree(cKDTree):
         ``fof(linking_length, min_members)`` numbers them: descending size,
         ties by the smaller head.  Returns a dict of arrays over the groups:
         ``head`` (smallest member row), ``size``, ``mass`` (sum of weights),
-        ``center`` float64 (G, 3) (wrapped into [0, L) on a periodic tree;
-        offsets are unwrapped relative to the head), ``rms_radius``, ``mean``
+        ``center`` float64 (G, 3) (wrapped into [0, L) on a periodic tree, L
+        the tree's float32 box, and still below L after a cast to float32, so
+        that it is a legal query of this tree: a coordinate within half a
+        float32 step below L is returned as 0, the same place; offsets are
+        unwrapped relative to the head), ``rms_radius``, ``mean``
         and ``dispersion`` (G, nv) of the value channels, ``spans_box`` (bool:
         a member lies L/2 or more from the head along an axis, so the
         unwrapped centre is not trustworthy; all False on a non-periodic
@@ -276,7 +279,9 @@ class KDTree(cKDTree):
         if self.periodic:
             L = float(self.boxsize)
             center = center % L
-            center[center >= L] = 0.0  # (a tiny negative wraps to L in float64)
+            # a tiny negative wraps to L in float64, and a centre within half a
+            # float32 step below L becomes L once cast: both are the place 0
+            center[center.astype(np.float32) >= np.float32(L)] = 0.0
             spans = dmax >= np.float32(0.5) * np.float32(self.boxsize)
         else:
             spans = np.zeros(head.shape[0], bool)
