@@ -92,6 +92,16 @@ constexpr int WPB = TB / 64;
 #ifndef NBKD_RETRY_MINV
 #define NBKD_RETRY_MINV 2.0f
 #endif
+//   NBKD_SCL_EARLY     the scan step reads the owner's bucket factor beside its
+//                      query and the point (three LDS reads in flight
+//                      together) instead of inside the hit branch, where it
+//                      was a fourth dependent LDS round trip of the step.
+//                      Off: collect 35.58 -> 35.48 ms per 1e8 queries, step
+//                      49.63 -> 49.61, inside the rounds' 0.3 ms spread
+//                      (profiles/r07a_walk_ab.txt)
+#ifndef NBKD_SCL_EARLY
+#define NBKD_SCL_EARLY 0
+#endif
 #ifndef NBKD_PAIR_PREFETCH
 #define NBKD_PAIR_PREFETCH 0 // (with NBKD_PAIR_PAD) the next step's pair entry read one step early
 #endif
@@ -189,22 +199,10 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                                            uint32_t (&st)[13]) {
     const float L = t.box;
     uint32_t last_cnt = 0;
-    uint32_t sk_node = 0;
-    int sp = 0;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
-    uint32_t node = 0;
-    float bx[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        bx[2 * a] = PER ? 0.0f : -FLT_MAX;
-        bx[2 * a + 1] = PER ? L : FLT_MAX;
-    }
-    float tm[3] = {box_lb_axis<M>(qx, bx[0], bx[1], L), box_lb_axis<M>(qy, bx[2], bx[3], L),
-                   box_lb_axis<M>(qz, bx[4], bx[5], L)};
-    uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= kth);
-    bool have = wm != 0;
-    nbkd_node nd = cnodes[0]; // record of `node` while `have`
+    PacketWalk wk;
+    walk_begin(wk);
     uint64_t tclk = STATS ? clock64() : 0;
 #define NBKD_PH(I)                                                                                 \
     do {                                                                                           \
@@ -214,242 +212,255 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
             tclk = t_;                                                                             \
         }                                                                                          \
     } while (0)
-    uint32_t pa = 0, ea = 0;
     // AHEAD: while a leaf's staging loads are in flight the walk goes on to the
     // next leaf (its node loads are scalar, lgkmcnt, so the staging's vmcnt wait
     // does not wait for them); the walk ahead prunes with the bounds from before
     // this leaf's scan, which are looser, so it may reach a leaf the tightened
     // bounds would skip: no lane then needs it (the per-leaf test below uses the
-    // current bounds), never a wrong result
-    bool ha_next = false;
-    uint32_t pa_next = 0, ea_next = 0, node_next = 0;
-    if constexpr (AHEAD) {
-        NBKD_GWALK(ha_next, pa_next, ea_next);
-        node_next = node;
-    }
+    // current bounds), never a wrong result.
+    // The loop is rotated so that the walk is expanded once per instance: an
+    // iteration walks to the next leaf, scans the leaf staged by the iteration
+    // before (AHEAD; none in the first), then stages the leaf it found.  The
+    // order stage(i), walk(i + 1), wait, scan(i) is the one the two call sites
+    // (before the loop and after the staging) gave.
+    bool ha = false;                   // AHEAD: a leaf is staged (pa, ea, lnode)
+    uint32_t pa = 0, ea = 0, lnode = 0;
     for (;;) {
-        bool ha;
-        uint32_t lnode;
-        if constexpr (AHEAD) {
-            ha = ha_next;
+        uint32_t pa_next = 0, ea_next = 0;
+        const bool ha_next = walk_next_leaf<M, STATS>(wk, cnodes, cboxes, qx, qy, qz, kth, L, pa_next,
+                                                      ea_next, st[0]);
+        if constexpr (!AHEAD) {
+            if (!ha_next) break;
+            ha = true;
             pa = pa_next;
             ea = ea_next;
-            lnode = node_next;
-        } else {
-            NBKD_GWALK(ha, pa, ea);
-            lnode = node;
+            lnode = wk.node;
         }
-        if (!ha) break;
-        if constexpr (STATS) ++st[3]; // leaves reached (staged), needed by some lane or not
-        // chunks: a leaf of 65..128 points is staged as its two halves, each
-        // with its own tight box (hinfo); other leaves in runs of 64 points
-        // under the leaf's tight box (leafinfo)
-        const uint32_t lend = ea;
-        const uint32_t lc = lend - pa;
-        const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
-        const uint32_t hm = (lc / 2) / 8 * 8;
-        const float *const lbox = halves ? hinfo + 12 * (size_t)lnode
-                                         : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode;
-        uint32_t c0 = pa;
-        uint32_t cn = halves ? hm : min((uint32_t)GCHUNK, lc);
-        NBKD_COLLECT_STAGE_G(pa, cn, lbox);
-        NBKD_PH(0);
-        if constexpr (AHEAD) {
-            NBKD_GWALK(ha_next, pa_next, ea_next);
-            node_next = node;
+        if (ha) {
+            // chunks: a leaf of 65..128 points is staged as its two halves, each
+            // with its own tight box (hinfo); other leaves in runs of 64 points
+            // under the leaf's tight box (leafinfo)
+            const uint32_t lend = ea;
+            const uint32_t lc = lend - pa;
+            const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
+            const uint32_t hm = (lc / 2) / 8 * 8;
+            const float *const lbox = halves ? hinfo + 12 * (size_t)lnode
+                                             : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode;
+            uint32_t c0 = pa;
+            uint32_t cn = halves ? hm : min((uint32_t)GCHUNK, lc);
+            if constexpr (!AHEAD) {
+                if constexpr (STATS) ++st[3]; // leaves reached (staged), needed by some lane or not
+                NBKD_COLLECT_STAGE_G(pa, cn, lbox);
+            }
             NBKD_PH(0);
-        }
-        // Tried and dropped (r04aa): pulling the next leaf's lines (points,
-        // group boxes, tight box) toward L2 here with one 4-B direct-to-LDS
-        // load per line, waiting vmcnt(1) for this leaf's staging only:
-        // collect 43.68 -> 46.97 ms per 1e8 (profiles/r04aa_ab_prefetch_anchor.txt)
-        wait_vm0();
-        wave_sync();
-        NBKD_PH(1);
-        bool any_leaf = false;
-        for (;;) {
-            const uint32_t ng = cn / NBKD_GROUP;
-            // the lanes whose ball reaches the leaf's tight box (leafinfo);
-            // ~12 of 64 on average at 1e8, so the group tests run compacted
-            const float tb[6] = {W.tb[0], W.tb[3], W.tb[1], W.tb[4], W.tb[2], W.tb[5]};
-            const bool need = box_lb2<M>(qx, qy, qz, tb, L) <= kth;
-            const uint64_t nm = __ballot(need);
-            if (nm != 0) {
-                any_leaf = true;
-                const uint32_t nneed = (uint32_t)__popcll(nm);
-                if constexpr (STATS) {
-                    st[2] += cn;
-                    st[12] += nneed;
-                }
-                W.cnt[lane] = cnt;
-                // the needing lanes' queries by compacted slot: 8 consecutive
-                // slots per 64 lanes below read 8 distinct, adjacent LDS words
-                // (indexed by lane, owners 16 apart hit the same banks)
-                if (need) {
-                    const uint32_t r = mbcnt64(nm);
-                    W.slot[r] = (uint8_t)lane;
-                    W.sq[r] = make_float4(qx, qy, qz, kth);
-                    W.scl[r] = nb_over_s;
-                }
-                wave_sync();
-                // (needing lane, group) box tests, 8 lanes per needing lane (one
-                // per group); the groups reached become the pair list, entries
-                // slot | owner lane << 6 | group << 12
-                uint32_t np = 0;
-                const uint32_t ntest = nneed * GMAX;
-#pragma unroll 1
-                for (uint32_t t0 = 0; t0 < ntest; t0 += 64) {
-                    const uint32_t ti = t0 + lane;
-                    const uint32_t g = ti % GMAX;
-                    const uint32_t sl = ti / GMAX;
-                    uint32_t owner = 0;
-                    bool hit = false;
-                    if (ti < ntest && g < ng) {
-                        owner = W.slot[sl];
-                        const float4 qq = W.sq[sl];
-                        const float gbx[6] = {W.gb[6 * g], W.gb[6 * g + 1], W.gb[6 * g + 2],
-                                              W.gb[6 * g + 3], W.gb[6 * g + 4], W.gb[6 * g + 5]};
-                        hit = box_lb2<M>(qq.x, qq.y, qq.z, gbx, L) <= qq.w;
-                    }
-                    const uint64_t hm = __ballot(hit);
-                    if (hit)
-                        W.pairs[np + mbcnt64(hm)] = (uint16_t)(sl | (owner << PR_OWNER) | (g << PR_G));
-                    np += (uint32_t)__popcll(hm);
-                }
-                if constexpr (STATS) st[5] += np * NBKD_GROUP; // (pair, point) evaluations
-#if NBKD_PAIR_PAD
-                // whole scan steps: the last one's missing pairs never hit
-                const uint32_t npp = (np + 7u) & ~7u;
-                if ((uint32_t)lane < npp - np) W.pairs[np + lane] = (uint16_t)PAIR_DUMMY;
-                np = npp;
-#endif
-                NBKD_PH(2);
-                wave_sync();
-                // Tried and dropped (r04s): the hit's column slot as the owner's
-                // count plus the hits below it in its run of lanes (the pair list
-                // is slot-major), with no returning LDS atomic and all of a step's
-                // LDS reads issued together: collect 46.7 -> 55.1 ms per 1e8
-                // queries (profiles/r04s_ab_seg_wide.txt); the 64-bit lane-mask
-                // arithmetic costs more issue than the atomics' waits.
-                // each pair's 8 points spread over 8 consecutive lanes
-                const uint32_t ntrip = np * NBKD_GROUP;
-#if NBKD_PAIR_PAD && NBKD_PAIR_PREFETCH
-                // the next step's pair entry is read while this step computes
-                uint32_t pr_next = ntrip ? W.pairs[(uint32_t)lane >> 3] : 0u;
-#endif
-#pragma unroll 1
-                for (uint32_t t0 = 0; t0 < ntrip; t0 += 64) {
-                    if constexpr (STATS) ++st[4];
-#if NBKD_PAIR_PAD
-                    // every lane of every step holds a pair (padding pairs never hit)
-                    {
-#if NBKD_PAIR_PREFETCH
-                        const uint32_t pr = pr_next;
-                        if (t0 + 64 < ntrip) pr_next = W.pairs[((t0 + 64) >> 3) + ((uint32_t)lane >> 3)];
-#else
-                        const uint32_t pr = W.pairs[(t0 >> 3) + ((uint32_t)lane >> 3)];
-#endif
-                        const uint32_t pi = (pr >> PR_G) * NBKD_GROUP + ((uint32_t)lane & 7u);
-#else
-                    const uint32_t ti = t0 + lane;
-                    if (ti < ntrip) {
-                        const uint32_t pr = W.pairs[ti / NBKD_GROUP];
-                        const uint32_t pi = (pr >> PR_G) * NBKD_GROUP + (ti % NBKD_GROUP);
-#endif
-                        const uint32_t qs = pr & PR_SLOT, owner = (pr >> PR_OWNER) & 63u;
-                        const float4 qq = W.sq[qs];
-                        const float4 pp = W.p4[pi];
-                        const float d = point_d2_fast<M>(qq.x, qq.y, qq.z, pp.x, pp.y, pp.z, L);
-#if NBKD_PAIR_ATOMIC
-                        // the hits of a pair (8 consecutive lanes, one owner):
-                        // ranked by mbcnt inside the 8-lane group, one returning
-                        // atomic by the group's last lane, its base broadcast by
-                        // two DPP moves (quad broadcast of lane 3, half-row mirror)
-                        const bool hit = d < qq.w;
-                        const uint64_t hm = __ballot(hit);
-                        const uint32_t gbits = (uint32_t)(hm >> ((uint32_t)lane & ~7u)) & 0xFFu;
-                        const uint32_t rank = __popc(gbits & ((1u << ((uint32_t)lane & 7u)) - 1u));
-                        uint32_t base = 0;
-                        if (((uint32_t)lane & 7u) == 7u && gbits != 0u)
-                            base = atomicAdd(&W.cnt[owner], (uint32_t)__popc(gbits));
-                        // quad_perm [3,3,3,3]: lanes 0-3 of the group read lane 3, 4-7 lane 7;
-                        // row_half_mirror into banks 0 and 2 only: lanes 0-3 read 7-4
-                        base = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)base, 0xFF, 0xF, 0xF, false);
-                        base = (uint32_t)__builtin_amdgcn_update_dpp((int)base, (int)base, 0x141, 0xF, 0x5,
-                                                                     false);
-                        if (hit) {
-                            const uint32_t j = d2_bucket(d, W.scl[qs]);
-                            atomicAdd(&W.hist[j >> 2][owner], 1u << (8 * (j & 3)));
-                            const uint32_t sl = base + rank;
-#else
-                        if (d < qq.w) {
-                            const uint32_t j = d2_bucket(d, W.scl[qs]);
-                            atomicAdd(&W.hist[j >> 2][owner], 1u << (8 * (j & 3)));
-                            const uint32_t sl = atomicAdd(&W.cnt[owner], 1u);
-#endif
-                            // a row past capg is a failure whose column is never read (both
-                            // selects): its extra hits overwrite its last slot (no branch)
-                            const uint32_t sw = min(sl, capg - 1u);
-                            // the candidate carries the point's original id (p4.w):
-                            // the selects write it without a gather
-                            // a 32-bit byte offset from the packet's (SGPR) column base:
-                            // one saddr store, no 64-bit address arithmetic per hit
-#if NBKD_COL_ROWMAJOR
-                            const uint32_t off = (__umul24(owner, capg) + sw) << 3;
-#else
-                            const uint32_t off = (((__umul24(sw >> 4, qpp) + owner) << 4) | (sw & 15u)) << 3;
-#endif
-                            *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(col) + off) =
-                                make_uint2(__float_as_uint(d), __float_as_uint(pp.w));
-                        }
-                    }
-                }
-                wave_sync();
-                cnt = W.cnt[lane];
-                NBKD_PH(4);
-            }
-            c0 += cn;
-            if (c0 >= lend) {
-                if constexpr (STATS) st[1] += any_leaf ? 1 : 0;
-                // tighten: smallest bucket edge with >= k candidates below it
-                // (after every leaf that added candidates; re-tightening only
-                // after 3 or 6 more was slower, 63.66 -> 64.00 / 63.98 ms per
-                // 1e8 step: the staler bound costs the select more than the
-                // skipped passes save, profiles/r04ag_ab_tighten_delta.txt)
-                const bool upd = cnt >= (uint32_t)kq && cnt != last_cnt;
-                if (__any(upd)) {
-                    wave_sync();
-                    if (upd) {
-                        last_cnt = cnt;
-                        const uint32_t p0 = W.hist[0][lane] * 0x01010101u;
-                        const uint32_t p1 = W.hist[1][lane] * 0x01010101u;
-                        const uint32_t p2 = W.hist[2][lane] * 0x01010101u;
-                        const uint32_t p3 = W.hist[3][lane] * 0x01010101u;
-                        const uint32_t c0w = p0 >> 24, c1w = c0w + (p1 >> 24), c2w = c1w + (p2 >> 24);
-                        const uint32_t kk = (uint32_t)kq;
-                        const uint32_t w = c0w >= kk ? 0u : c1w >= kk ? 1u : c2w >= kk ? 2u : 3u;
-                        const uint32_t base = w == 0 ? 0u : w == 1 ? c0w : w == 2 ? c1w : c2w;
-                        const uint32_t pw = w == 0 ? p0 : w == 1 ? p1 : w == 2 ? p2 : p3;
-                        const uint32_t need_k = kk - base;
-                        const uint32_t nb = (((pw & 0xFFu) < need_k) ? 1u : 0u) +
-                                            ((((pw >> 8) & 0xFFu) < need_k) ? 1u : 0u) +
-                                            ((((pw >> 16) & 0xFFu) < need_k) ? 1u : 0u) +
-                                            (((pw >> 24) < need_k) ? 1u : 0u);
-                        const uint32_t jstar = 4 * w + nb;
-                        if (jstar < (uint32_t)(NB - 1))
-                            kth = fminf(kth, (float)(jstar + 1) * s_over_nb);
-                    }
-                }
-                NBKD_PH(5);
-                break;
-            }
-            cn = halves ? lc - hm : min((uint32_t)GCHUNK, lend - c0);
-            wave_sync();
-            NBKD_COLLECT_STAGE_G(c0, cn, halves ? lbox + 6 : lbox);
+            // Tried and dropped (r04aa): pulling the next leaf's lines (points,
+            // group boxes, tight box) toward L2 here with one 4-B direct-to-LDS
+            // load per line, waiting vmcnt(1) for this leaf's staging only:
+            // collect 43.68 -> 46.97 ms per 1e8 (profiles/r04aa_ab_prefetch_anchor.txt)
             wait_vm0();
             wave_sync();
+            NBKD_PH(1);
+            bool any_leaf = false;
+            for (;;) {
+                const uint32_t ng = cn / NBKD_GROUP;
+                // the lanes whose ball reaches the leaf's tight box (leafinfo);
+                // ~12 of 64 on average at 1e8, so the group tests run compacted
+                const float tb[6] = {W.tb[0], W.tb[3], W.tb[1], W.tb[4], W.tb[2], W.tb[5]};
+                const bool need = box_lb2<M>(qx, qy, qz, tb, L) <= kth;
+                const uint64_t nm = __ballot(need);
+                if (nm != 0) {
+                    any_leaf = true;
+                    const uint32_t nneed = (uint32_t)__popcll(nm);
+                    if constexpr (STATS) {
+                        st[2] += cn;
+                        st[12] += nneed;
+                    }
+                    W.cnt[lane] = cnt;
+                    // the needing lanes' queries by compacted slot: 8 consecutive
+                    // slots per 64 lanes below read 8 distinct, adjacent LDS words
+                    // (indexed by lane, owners 16 apart hit the same banks)
+                    if (need) {
+                        const uint32_t r = mbcnt64(nm);
+                        W.slot[r] = (uint8_t)lane;
+                        W.sq[r] = make_float4(qx, qy, qz, kth);
+                        W.scl[r] = nb_over_s;
+                    }
+                    wave_sync();
+                    // (needing lane, group) box tests, 8 lanes per needing lane (one
+                    // per group); the groups reached become the pair list, entries
+                    // slot | owner lane << 6 | group << 12
+                    uint32_t np = 0;
+                    const uint32_t ntest = nneed * GMAX;
+#pragma unroll 1
+                    for (uint32_t t0 = 0; t0 < ntest; t0 += 64) {
+                        const uint32_t ti = t0 + lane;
+                        const uint32_t g = ti % GMAX;
+                        const uint32_t sl = ti / GMAX;
+                        uint32_t owner = 0;
+                        bool hit = false;
+                        if (ti < ntest && g < ng) {
+                            owner = W.slot[sl];
+                            const float4 qq = W.sq[sl];
+                            const float gbx[6] = {W.gb[6 * g], W.gb[6 * g + 1], W.gb[6 * g + 2],
+                                                  W.gb[6 * g + 3], W.gb[6 * g + 4], W.gb[6 * g + 5]};
+                            hit = box_lb2<M>(qq.x, qq.y, qq.z, gbx, L) <= qq.w;
+                        }
+                        const uint64_t hm = __ballot(hit);
+                        if (hit)
+                            W.pairs[np + mbcnt64(hm)] = (uint16_t)(sl | (owner << PR_OWNER) | (g << PR_G));
+                        np += (uint32_t)__popcll(hm);
+                    }
+                    if constexpr (STATS) st[5] += np * NBKD_GROUP; // (pair, point) evaluations
+#if NBKD_PAIR_PAD
+                    // whole scan steps: the last one's missing pairs never hit
+                    const uint32_t npp = (np + 7u) & ~7u;
+                    if ((uint32_t)lane < npp - np) W.pairs[np + lane] = (uint16_t)PAIR_DUMMY;
+                    np = npp;
+#endif
+                    NBKD_PH(2);
+                    wave_sync();
+                    // Tried and dropped (r04s): the hit's column slot as the owner's
+                    // count plus the hits below it in its run of lanes (the pair list
+                    // is slot-major), with no returning LDS atomic and all of a step's
+                    // LDS reads issued together: collect 46.7 -> 55.1 ms per 1e8
+                    // queries (profiles/r04s_ab_seg_wide.txt); the 64-bit lane-mask
+                    // arithmetic costs more issue than the atomics' waits.
+                    // each pair's 8 points spread over 8 consecutive lanes
+                    const uint32_t ntrip = np * NBKD_GROUP;
+#if NBKD_PAIR_PAD && NBKD_PAIR_PREFETCH
+                    // the next step's pair entry is read while this step computes
+                    uint32_t pr_next = ntrip ? W.pairs[(uint32_t)lane >> 3] : 0u;
+#endif
+#pragma unroll 1
+                    for (uint32_t t0 = 0; t0 < ntrip; t0 += 64) {
+                        if constexpr (STATS) ++st[4];
+#if NBKD_PAIR_PAD
+                        // every lane of every step holds a pair (padding pairs never hit)
+                        {
+#if NBKD_PAIR_PREFETCH
+                            const uint32_t pr = pr_next;
+                            if (t0 + 64 < ntrip) pr_next = W.pairs[((t0 + 64) >> 3) + ((uint32_t)lane >> 3)];
+#else
+                            const uint32_t pr = W.pairs[(t0 >> 3) + ((uint32_t)lane >> 3)];
+#endif
+                            const uint32_t pi = (pr >> PR_G) * NBKD_GROUP + ((uint32_t)lane & 7u);
+#else
+                        const uint32_t ti = t0 + lane;
+                        if (ti < ntrip) {
+                            const uint32_t pr = W.pairs[ti / NBKD_GROUP];
+                            const uint32_t pi = (pr >> PR_G) * NBKD_GROUP + (ti % NBKD_GROUP);
+#endif
+                            const uint32_t qs = pr & PR_SLOT, owner = (pr >> PR_OWNER) & 63u;
+                            const float4 qq = W.sq[qs];
+                            const float4 pp = W.p4[pi];
+                            float scl_e = 0.0f; // NBKD_SCL_EARLY: in flight with the query and the point
+                            if constexpr (NBKD_SCL_EARLY != 0) scl_e = W.scl[qs];
+                            const float d = point_d2_fast<M>(qq.x, qq.y, qq.z, pp.x, pp.y, pp.z, L);
+#if NBKD_PAIR_ATOMIC
+                            // the hits of a pair (8 consecutive lanes, one owner):
+                            // ranked by mbcnt inside the 8-lane group, one returning
+                            // atomic by the group's last lane, its base broadcast by
+                            // two DPP moves (quad broadcast of lane 3, half-row mirror)
+                            const bool hit = d < qq.w;
+                            const uint64_t hm = __ballot(hit);
+                            const uint32_t gbits = (uint32_t)(hm >> ((uint32_t)lane & ~7u)) & 0xFFu;
+                            const uint32_t rank = __popc(gbits & ((1u << ((uint32_t)lane & 7u)) - 1u));
+                            uint32_t base = 0;
+                            if (((uint32_t)lane & 7u) == 7u && gbits != 0u)
+                                base = atomicAdd(&W.cnt[owner], (uint32_t)__popc(gbits));
+                            // quad_perm [3,3,3,3]: lanes 0-3 of the group read lane 3, 4-7 lane 7;
+                            // row_half_mirror into banks 0 and 2 only: lanes 0-3 read 7-4
+                            base = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)base, 0xFF, 0xF, 0xF, false);
+                            base = (uint32_t)__builtin_amdgcn_update_dpp((int)base, (int)base, 0x141, 0xF, 0x5,
+                                                                         false);
+                            if (hit) {
+                                const uint32_t j = d2_bucket(d, NBKD_SCL_EARLY ? scl_e : W.scl[qs]);
+                                atomicAdd(&W.hist[j >> 2][owner], 1u << (8 * (j & 3)));
+                                const uint32_t sl = base + rank;
+#else
+                            if (d < qq.w) {
+                                const uint32_t j = d2_bucket(d, NBKD_SCL_EARLY ? scl_e : W.scl[qs]);
+                                atomicAdd(&W.hist[j >> 2][owner], 1u << (8 * (j & 3)));
+                                const uint32_t sl = atomicAdd(&W.cnt[owner], 1u);
+#endif
+                                // a row past capg is a failure whose column is never read (both
+                                // selects): its extra hits overwrite its last slot (no branch)
+                                const uint32_t sw = min(sl, capg - 1u);
+                                // the candidate carries the point's original id (p4.w):
+                                // the selects write it without a gather
+                                // a 32-bit byte offset from the packet's (SGPR) column base:
+                                // one saddr store, no 64-bit address arithmetic per hit
+#if NBKD_COL_ROWMAJOR
+                                const uint32_t off = (__umul24(owner, capg) + sw) << 3;
+#else
+                                const uint32_t off = (((__umul24(sw >> 4, qpp) + owner) << 4) | (sw & 15u)) << 3;
+#endif
+                                *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(col) + off) =
+                                    make_uint2(__float_as_uint(d), __float_as_uint(pp.w));
+                            }
+                        }
+                    }
+                    wave_sync();
+                    cnt = W.cnt[lane];
+                    NBKD_PH(4);
+                }
+                c0 += cn;
+                if (c0 >= lend) {
+                    if constexpr (STATS) st[1] += any_leaf ? 1 : 0;
+                    // tighten: smallest bucket edge with >= k candidates below it
+                    // (after every leaf that added candidates; re-tightening only
+                    // after 3 or 6 more was slower, 63.66 -> 64.00 / 63.98 ms per
+                    // 1e8 step: the staler bound costs the select more than the
+                    // skipped passes save, profiles/r04ag_ab_tighten_delta.txt)
+                    const bool upd = cnt >= (uint32_t)kq && cnt != last_cnt;
+                    if (__any(upd)) {
+                        wave_sync();
+                        if (upd) {
+                            last_cnt = cnt;
+                            const uint32_t p0 = W.hist[0][lane] * 0x01010101u;
+                            const uint32_t p1 = W.hist[1][lane] * 0x01010101u;
+                            const uint32_t p2 = W.hist[2][lane] * 0x01010101u;
+                            const uint32_t p3 = W.hist[3][lane] * 0x01010101u;
+                            const uint32_t c0w = p0 >> 24, c1w = c0w + (p1 >> 24), c2w = c1w + (p2 >> 24);
+                            const uint32_t kk = (uint32_t)kq;
+                            const uint32_t w = c0w >= kk ? 0u : c1w >= kk ? 1u : c2w >= kk ? 2u : 3u;
+                            const uint32_t base = w == 0 ? 0u : w == 1 ? c0w : w == 2 ? c1w : c2w;
+                            const uint32_t pw = w == 0 ? p0 : w == 1 ? p1 : w == 2 ? p2 : p3;
+                            const uint32_t need_k = kk - base;
+                            const uint32_t nb = (((pw & 0xFFu) < need_k) ? 1u : 0u) +
+                                                ((((pw >> 8) & 0xFFu) < need_k) ? 1u : 0u) +
+                                                ((((pw >> 16) & 0xFFu) < need_k) ? 1u : 0u) +
+                                                (((pw >> 24) < need_k) ? 1u : 0u);
+                            const uint32_t jstar = 4 * w + nb;
+                            if (jstar < (uint32_t)(NB - 1))
+                                kth = fminf(kth, (float)(jstar + 1) * s_over_nb);
+                        }
+                    }
+                    NBKD_PH(5);
+                    break;
+                }
+                cn = halves ? lc - hm : min((uint32_t)GCHUNK, lend - c0);
+                wave_sync();
+                NBKD_COLLECT_STAGE_G(c0, cn, halves ? lbox + 6 : lbox);
+                wait_vm0();
+                wave_sync();
+            }
+            wave_sync();
         }
-        wave_sync();
+        if constexpr (AHEAD) {
+            if (!ha_next) break;
+            // stage the leaf found; the next iteration walks on while it loads
+            ha = true;
+            pa = pa_next;
+            ea = ea_next;
+            lnode = wk.node;
+            if constexpr (STATS) ++st[3];
+            const uint32_t lc = ea - pa;
+            const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
+            NBKD_COLLECT_STAGE_G(pa, halves ? (lc / 2) / 8 * 8 : min((uint32_t)GCHUNK, lc),
+                                 halves ? hinfo + 12 * (size_t)lnode
+                                        : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode);
+        }
     }
     NBKD_PH(0);
 #undef NBKD_PH

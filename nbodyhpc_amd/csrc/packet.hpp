@@ -110,7 +110,9 @@ struct PadLeaves {
 };
 
 // ------------------------------------------------------------------ packet walk
-// The wave's depth-first walk (knn_collect.hip, ball.hip).  The macros expect in
+// The wave's depth-first walk as macros (ball.hip, ball_hist.hip, ball_sum.hip,
+// ball_profile.hip, fof.hip; the kNN collect uses the scalar-resident form of
+// the same traversal further down, walk_next_leaf).  The macros expect in
 // scope: lane, qx/qy/qz, the bound kth, L, cnodes, the walk state node / nd (its
 // record while `have`) / have / wm / bx[6] / tm[3], the wave stack sp / sk_node,
 // the cell boxes cboxes, the metric switch M and STATS / st (node visits in
@@ -235,6 +237,171 @@ typedef const NodeBox *cbox_ptr;
         else                                                                                       \
             NBKD_GSTEP(2)                                                                          \
     }
+
+// ------------------------------------------------------------------ scalar-resident walk
+// The same traversal as NBKD_GWALK / NBKD_GSTEP (same bound arithmetic in the
+// same order, same near-first vote, same pushes and pop tests, so the same
+// leaf sequence), for the kNN collect, in a form the compiler keeps scalar:
+//   - the node record's four words, the popped id and the popped box are
+//     pinned to SGPRs where they are loaded (readfirstlane of a value that is
+//     uniform already costs nothing), and the box is kept as bit patterns:
+//     a uniform select of integers is an s_cselect, one of floats a
+//     v_cndmask that drags the whole box into VGPRs.  The leaf test and the
+//     axis dispatch are s_cmp on SGPRs, the split a scalar VALU operand;
+//   - one loop with one exit.  The compiler gives every loop with several
+//     exits (a return or break out of a nested step, the FOUND protocol) a
+//     guard variable and re-dispatches on it after the loop, and carries the
+//     `have` flag as a 64-bit lane mask from block to block.  Here the state
+//     is explicit and scalar: the node, whether its record is loaded, and
+//     the stack pointer; an iteration pops (when no record is loaded) and
+//     then looks at one record, and ends in exactly one of enter child, pop,
+//     leaf found, done;
+//   - every call starts with a pop: the root is pushed before the first call
+//     (walk_begin), and its cell box cboxes[0] is the root box the macro form
+//     starts from, so its bounds and wanted mask have the same bits;
+//   - a pop issues the node's record load beside its box load, one wait for
+//     both (for a popped node no lane wants any more that is 16 B of scalar
+//     cache traffic for nothing; the record is not looked at).
+// The axis dispatch stays a scalar three-way branch over three step bodies
+// with a compile-time axis.  Tried and dropped: one body whose split-axis
+// coordinate, box faces and bound term are picked by scalar-controlled
+// selects (10 branches and 42 VALU in the plain walk loop instead of 21 and
+// 70): step 52.61 ms against 51.29 with three bodies and 52.83 for the macro
+// walk, same rows (profiles/r07a_walk_ab.txt).
+
+struct PacketWalk {
+    uint32_t node;    // the node the walk stands on (after a found leaf: its id)
+    int sp;           // entries on the wave stack
+    uint32_t sk_node; // the wave stack: entry i in lane i
+    uint32_t bx[6];   // the cell box of `node`, as float bits (SGPRs)
+    float tm[3];      // per lane: the box's per-axis bound terms
+};
+
+// the walk stands before the root: one stack entry, node 0 (in lane 0)
+__device__ __forceinline__ void walk_begin(PacketWalk &w) {
+    w.node = 0;
+    w.sp = 1;
+    w.sk_node = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) w.bx[a] = 0u;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) w.tm[a] = 0.0f;
+}
+
+// One internal node with split axis D (a constant after inlining): true = the walk entered a child (w.node, its box, bounds and
+// wanted mask wm); false = no lane wants either child, the state is dead and
+// the next pop rewrites all of it.
+template <bool M>
+__device__ __forceinline__ bool walk_step(PacketWalk &w, const int D, const uint32_t split_bits,
+                                          const uint32_t left, const uint32_t right, uint64_t &wm,
+                                          const float qx, const float qy, const float qz,
+                                          const float kth, const float L) {
+    const float split = __uint_as_float(split_bits);
+    const float qd = D == 0 ? qx : (D == 1 ? qy : qz);
+    float tl, tr;
+    if constexpr (M) {
+        const uint32_t lo = D == 0 ? w.bx[0] : (D == 1 ? w.bx[2] : w.bx[4]);
+        const uint32_t hi = D == 0 ? w.bx[1] : (D == 1 ? w.bx[3] : w.bx[5]);
+        tl = box_lb_axis<M>(qd, __uint_as_float(lo), split, L);
+        tr = box_lb_axis<M>(qd, split, __uint_as_float(hi), L);
+    } else {
+        // plain: the child on q's side keeps the slab's bound tm[D] (the same
+        // bits box_lb_axis gives), the other one is (q - split)^2
+        const float tmd = D == 0 ? w.tm[0] : (D == 1 ? w.tm[1] : w.tm[2]);
+        const float dd = qd - split;
+        const float m2 = dd * dd;
+        tl = dd > 0.0f ? m2 : tmd;
+        tr = dd > 0.0f ? tmd : m2;
+    }
+    const float dl = ((D == 0 ? tl : w.tm[0]) + (D == 1 ? tl : w.tm[1])) + (D == 2 ? tl : w.tm[2]);
+    const float dr = ((D == 0 ? tr : w.tm[0]) + (D == 1 ? tr : w.tm[1])) + (D == 2 ? tr : w.tm[2]);
+    const uint64_t wl = __ballot(dl <= kth), wr = __ballot(dr <= kth);
+    bool go_right = wr != 0;
+    // both wanted: the lanes that want the node vote which child is near
+    // (entered) and which far (pushed)
+    if (wl != 0 && wr != 0) {
+        const uint32_t right_votes = (uint32_t)__popcll(wm & __ballot(qd > split));
+        go_right = 2 * right_votes > (uint32_t)__popcll(wm);
+        w.sk_node = lane_set(w.sk_node, go_right ? left : right, 1ull << w.sp);
+        ++w.sp;
+    }
+    w.node = go_right ? right : left;
+    const float tn = go_right ? tr : tl;
+    w.tm[0] = D == 0 ? tn : w.tm[0];
+    w.tm[1] = D == 1 ? tn : w.tm[1];
+    w.tm[2] = D == 2 ? tn : w.tm[2];
+    // the entered child's box: the split replaces the face on the other side
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        w.bx[2 * a] = (D == a && go_right) ? split_bits : w.bx[2 * a];
+        w.bx[2 * a + 1] = (D == a && !go_right) ? split_bits : w.bx[2 * a + 1];
+    }
+    wm = go_right ? wr : wl;
+    return (wl | wr) != 0;
+}
+
+// advance the walk to the next leaf some lane wants: true = leaf w.node holds
+// the points [lpos, lend); false = the walk is over.  visits counts the node
+// records looked at (the work counter node_visits).
+template <bool M, bool STATS>
+__device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cnodes,
+                                               const cbox_ptr cboxes, const float qx,
+                                               const float qy, const float qz, const float kth,
+                                               const float L, uint32_t &lpos, uint32_t &lend,
+                                               uint32_t &visits) {
+    enum : int { RUN = 0, LEAF = 1, DONE = 2 };
+    bool loaded = false; // the record of w.node is in nd
+    int end = RUN;
+    int dim = 0;
+    uint32_t split_bits = 0, left = 0, right = 0;
+    uint64_t wm = 0;
+    do {
+        if (!loaded) {
+            if (w.sp == 0) {
+                end = DONE;
+            } else {
+                --w.sp;
+                w.node = (uint32_t)__builtin_amdgcn_readlane((int)w.sk_node, w.sp);
+                const NodeBox nb = cboxes[w.node];
+                const nbkd_node nd = cnodes[w.node];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) w.bx[a] = uni(__float_as_uint(nb.b[a]));
+                dim = (int)uni((uint32_t)nd.dimension);
+                split_bits = uni(__float_as_uint(nd.split));
+                left = uni(nd.left);
+                right = uni(nd.right);
+                w.tm[0] = box_lb_axis<M>(qx, __uint_as_float(w.bx[0]), __uint_as_float(w.bx[1]), L);
+                w.tm[1] = box_lb_axis<M>(qy, __uint_as_float(w.bx[2]), __uint_as_float(w.bx[3]), L);
+                w.tm[2] = box_lb_axis<M>(qz, __uint_as_float(w.bx[4]), __uint_as_float(w.bx[5]), L);
+                wm = __ballot((w.tm[0] + w.tm[1]) + w.tm[2] <= kth);
+                loaded = wm != 0;
+            }
+        }
+        if (loaded) {
+            if constexpr (STATS) ++visits;
+            if (dim < 0) {
+                lpos = left;
+                lend = right;
+                end = LEAF;
+            } else {
+                if (dim == 0)
+                    loaded = walk_step<M>(w, 0, split_bits, left, right, wm, qx, qy, qz, kth, L);
+                else if (dim == 1)
+                    loaded = walk_step<M>(w, 1, split_bits, left, right, wm, qx, qy, qz, kth, L);
+                else
+                    loaded = walk_step<M>(w, 2, split_bits, left, right, wm, qx, qy, qz, kth, L);
+                // the child's record (asked for also when no child was
+                // entered: no branch, and the pop that follows overwrites it)
+                const nbkd_node nd = cnodes[w.node];
+                dim = (int)uni((uint32_t)nd.dimension);
+                split_bits = uni(__float_as_uint(nd.split));
+                left = uni(nd.left);
+                right = uni(nd.right);
+            }
+        }
+    } while (end == RUN);
+    return end == LEAF;
+}
 
 } // namespace dev
 } // namespace nbkd
