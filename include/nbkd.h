@@ -656,9 +656,17 @@ void nbkd_free(nbkd_tree *tree);
  *                      the caller's pageable arrays and the device instead
  *                      (same results, lower rate).  Idle workspaces release
  *                      their staging when a device allocation needs memory.
+ *   "collect_wide_addr" 0 (default): the kNN collect kernel's tree walk loads
+ *                      node records and cell boxes at 32-bit byte offsets from
+ *                      the table bases wherever every offset fits (fewer than
+ *                      2^27 nodes); 1: always through 64-bit addresses, the
+ *                      instance larger trees take.  Results never depend on it.
  * NEW (no reference counterpart: kdtree/src/cpp/pybind.cpp:196-216 has no knobs). */
 nbkd_status nbkd_set_tuning(const char *name, double value);
 nbkd_status nbkd_get_tuning(const char *name, double *value);
+/* 1 if a tree of `nodes` nodes takes the collect kernel's wide-address
+ * instance under the current "collect_wide_addr" setting, else 0.  NEW. */
+int32_t nbkd_collect_wide_addr(uint64_t nodes);
 
 /* The calling thread's interrupt check: host-buffer query calls (kNN, k-th
  * distance, radius count) call fn(user) between batches and stop with

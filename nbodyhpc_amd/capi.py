@@ -96,6 +96,7 @@ _PROTOS = {
     "nbkd_set_tuning": (_i32, [ctypes.c_char_p, ctypes.c_double]),
     "nbkd_set_interrupt": (_i32, [_c_p, _c_p]),
     "nbkd_get_tuning": (_i32, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]),
+    "nbkd_collect_wide_addr": (_i32, [_u64]),
     "nbkd_comm_probe": (_i32, []),
     "nbkd_comm_unique_id": (_i32, [_c_p]),
     "nbkd_comm_init": (_i32, [_c_p, _i32, _i32, _i32, ctypes.POINTER(_c_p)]),
@@ -587,6 +588,12 @@ def get_tuning(name):
     v = ctypes.c_double()
     _check(lib().nbkd_get_tuning(name.encode(), ctypes.byref(v)))
     return v.value
+
+
+def collect_wide_addr(nodes):
+    """nbkd_collect_wide_addr: whether a tree of `nodes` nodes takes the collect
+    kernel's wide-address instance (the "collect_wide_addr" knob forces it)."""
+    return bool(lib().nbkd_collect_wide_addr(int(nodes)))
 
 
 def timing_enable(on=True):

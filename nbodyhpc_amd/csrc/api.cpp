@@ -269,9 +269,10 @@ void tree_free(void *p) {
 
 namespace {
 // nbkd_set_tuning knobs (process-wide); defaults are the measured optima
-std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0}, {0.0}};
+std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0}, {0.0}, {0.0}};
 const char *const g_tune_names[TUNE_N] = {"knn_seed_margin", "candidate_bytes", "host_batch",
-                                          "host_threads", "self_order", "pinned_bytes"};
+                                          "host_threads", "self_order", "pinned_bytes",
+                                          "collect_wide_addr"};
 thread_local nbkd_interrupt_fn t_intr = nullptr;
 thread_local void *t_intr_user = nullptr;
 } // namespace
@@ -1034,6 +1035,8 @@ nbkd_status nbkd_set_tuning(const char *name, double value) {
     set_error(std::string("nbkd_set_tuning: unknown knob ") + name);
     return NBKD_EINVAL;
 }
+
+int32_t nbkd_collect_wide_addr(uint64_t nodes) { return collect_wide_addr(nodes) ? 1 : 0; }
 
 nbkd_status nbkd_get_tuning(const char *name, double *value) {
     if (!name || !value) {

@@ -235,6 +235,7 @@ enum TuneId {
     TUNE_HOST_THREADS,
     TUNE_SELF_ORDER,
     TUNE_PINNED_BYTES,
+    TUNE_COLLECT_WIDE,
     TUNE_N
 };
 // host memcpy split over the library's copy threads (api.cpp): the host-buffer
@@ -361,6 +362,11 @@ __device__ __forceinline__ uint32_t span_m(const QSpan &s) {
 // ids, or as sorted positions pos_base + i when pos_base != ~0u; retry names
 // the timers)
 uint32_t collect_capacity(int k);
+// true: a tree of nnodes nodes takes the collect kernel's instance whose walk
+// loads node records and cell boxes through 64-bit addresses; false: the one
+// with 32-bit offsets (every box offset, id * 32 B, then fits 32 bits).
+// nbkd_set_tuning("collect_wide_addr", 1) forces the wide one.
+bool collect_wide_addr(uint64_t nnodes);
 // seed-failure retry: adaptive per-query seeds written by the first select
 // pass (on by default) instead of a fixed 4x seed
 bool retry_adaptive();

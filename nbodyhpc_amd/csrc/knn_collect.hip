@@ -102,6 +102,16 @@ constexpr int WPB = TB / 64;
 #ifndef NBKD_SCL_EARLY
 #define NBKD_SCL_EARLY 0
 #endif
+//   NBKD_WALK_ASM      the plain-metric walk of a tree whose node offsets fit
+//                      32 bits descends in the hand-scheduled block of
+//                      packet.hpp (walk_descend) instead of the compiled loop:
+//                      SALU per packet 9.94k -> 7.72k, collect 35.71 -> 33.62 ms
+//                      per 1e8 queries, step 50.01 -> 47.78, same rows
+//                      (profiles/r08a_collect_ab.txt; the 32-bit offsets alone,
+//                      =0: 35.53 against 35.64)
+#ifndef NBKD_WALK_ASM
+#define NBKD_WALK_ASM 1
+#endif
 #ifndef NBKD_PAIR_PREFETCH
 #define NBKD_PAIR_PREFETCH 0 // (with NBKD_PAIR_PAD) the next step's pair entry read one step early
 #endif
@@ -187,7 +197,7 @@ struct CollectLdsG {
 // st: node visits, leaves scanned, points staged, leaves reached, sparse
 // iterations, pair evaluations, then 6 phase clocks, then lanes needing a
 // staged chunk summed over chunks (STATS only)
-template <bool PER, bool M, bool STATS, bool AHEAD>
+template <bool PER, bool M, bool STATS, bool AHEAD, bool NARROW>
 __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__restrict__ ginfo,
                                            const uint32_t *__restrict__ linfo,
                                            const float *__restrict__ hinfo,
@@ -227,8 +237,13 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
     uint32_t pa = 0, ea = 0, lnode = 0;
     for (;;) {
         uint32_t pa_next = 0, ea_next = 0;
-        const bool ha_next = walk_next_leaf<M, STATS>(wk, cnodes, cboxes, qx, qy, qz, kth, L, pa_next,
-                                                      ea_next, st[0]);
+        bool ha_next;
+        if constexpr (NBKD_WALK_ASM != 0 && !M && NARROW)
+            ha_next = walk_next_leaf_plain<STATS>(wk, cnodes, cboxes, qx, qy, qz, kth, L, pa_next,
+                                                  ea_next, st[0]);
+        else
+            ha_next = walk_next_leaf<M, STATS, NARROW>(wk, cnodes, cboxes, qx, qy, qz, kth, L,
+                                                       pa_next, ea_next, st[0]);
         if constexpr (!AHEAD) {
             if (!ha_next) break;
             ha = true;
@@ -467,7 +482,7 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
 }
 
 // one packet of the collect pass
-template <bool PER, bool STATS, bool AHEAD>
+template <bool PER, bool STATS, bool AHEAD, bool NARROW>
 __device__ __forceinline__ void collect_packet(
     const DevTree &t, const float *__restrict__ ginfo, const uint32_t *__restrict__ linfo,
     const float *__restrict__ hinfo, const float *__restrict__ q, const uint32_t *__restrict__ order,
@@ -521,10 +536,10 @@ __device__ __forceinline__ void collect_packet(
         plain = __all(wf);
     }
     if (plain)
-        grp_packet<PER, false, STATS, AHEAD>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, false, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                              s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     else
-        grp_packet<PER, PER, STATS, AHEAD>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                            s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     if (valid) ccount[gq] = cnt;
     // the final bound: at least k candidates lie strictly below it (bound
@@ -553,7 +568,7 @@ __device__ __forceinline__ void collect_packet(
 // A static pass launches one wave per packet; a device-counted pass (the
 // retry rounds: LOOP) a fixed grid that strides over its packets.  Only the
 // LOOP instance carries the loop (in the first pass it cost a 12-28 B spill).
-template <bool PER, int OCC, bool STATS, bool LOOP, bool AHEAD>
+template <bool PER, int OCC, bool STATS, bool LOOP, bool AHEAD, bool NARROW>
 __global__ void __launch_bounds__(TB, OCC)
 knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
                        const uint32_t *__restrict__ linfo, const float *__restrict__ hinfo,
@@ -572,14 +587,14 @@ knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
     if constexpr (LOOP) {
         for (uint32_t pk = bid * WPB + wave; pk < npk; pk += gridDim.x * WPB) {
             wave_sync(); // the previous packet's LDS reads are done
-            collect_packet<PER, STATS, AHEAD>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
         }
     } else {
         const uint32_t pk = bid * WPB + wave;
         if (pk < npk)
-            collect_packet<PER, STATS, AHEAD>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
     }
@@ -1313,10 +1328,19 @@ void launch_collect(const Tree &t, const float *q, const uint32_t *order, QSpan 
         }();
         // the re-walk rounds are timed as one phase by the caller (query.hip)
         TimedScope ts(name, s, !retry);
-#define NBKD_GRP(STATS, LOOP, AHEAD, STP, XCD)                                                     \
-    knn_collect_grp_kernel<PER, 8, STATS, LOOP, AHEAD><<<blocks, TB, 0, s>>>(                      \
+        // the walk's node and box loads take 32-bit offsets wherever the tree allows
+        const bool narrow = !collect_wide_addr((uint64_t)t.nnodes);
+#define NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, NARROW)                                            \
+    knn_collect_grp_kernel<PER, 8, STATS, LOOP, AHEAD, NARROW><<<blocks, TB, 0, s>>>(              \
         view(t), t.ginfo, t.leafinfo, t.hinfo, q, order, span, k, tg, seed_mul, qpp, cand, capg,   \
         ccount, STP, XCD, kbound)
+#define NBKD_GRP(STATS, LOOP, AHEAD, STP, XCD)                                                     \
+    do {                                                                                           \
+        if (narrow)                                                                                \
+            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, true);                                         \
+        else                                                                                       \
+            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, false);                                        \
+    } while (0)
         if (span.count)
             NBKD_GRP(false, true, NBKD_LOOP_AHEAD != 0, nullptr, false);
         else if (collect_ahead()) {
@@ -1329,6 +1353,7 @@ void launch_collect(const Tree &t, const float *q, const uint32_t *order, QSpan 
         else
             NBKD_GRP(false, false, false, nullptr, xcd);
 #undef NBKD_GRP
+#undef NBKD_GRP_
         return;
     }
 }
@@ -1430,6 +1455,10 @@ bool retry_adaptive() {
         return !(e && atoi(e) == 0);
     }();
     return on;
+}
+
+bool collect_wide_addr(uint64_t nnodes) {
+    return !dev::walk_narrow_ok(nnodes) || tuning(TUNE_COLLECT_WIDE) != 0.0;
 }
 
 uint32_t collect_capacity(int k) {

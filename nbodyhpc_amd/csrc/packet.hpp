@@ -288,6 +288,36 @@ __device__ __forceinline__ void walk_begin(PacketWalk &w) {
     for (int a = 0; a < 3; ++a) w.tm[a] = 0.0f;
 }
 
+// A node's record or cell box through the scalar cache.  NARROW: the byte
+// offset is formed in 32 bits (one s_lshl_b32) and given to the load as its
+// SGPR offset beside the table's base; otherwise the load takes a 64-bit
+// address (a 64-bit shift, an add and an add with carry).  NARROW needs every
+// node's box offset, id * 32 B, to fit 32 bits (walk_narrow_ok).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) char *cbyte_ptr;
+#else
+typedef const char *cbyte_ptr;
+#endif
+template <bool NARROW>
+__device__ __forceinline__ nbkd_node walk_load_node(const cnode_ptr cnodes, const uint32_t id) {
+    if constexpr (NARROW)
+        return *reinterpret_cast<cnode_ptr>(reinterpret_cast<cbyte_ptr>(cnodes) +
+                                            id * (uint32_t)sizeof(nbkd_node));
+    else
+        return cnodes[id];
+}
+template <bool NARROW>
+__device__ __forceinline__ NodeBox walk_load_box(const cbox_ptr cboxes, const uint32_t id) {
+    if constexpr (NARROW)
+        return *reinterpret_cast<cbox_ptr>(reinterpret_cast<cbyte_ptr>(cboxes) +
+                                           id * (uint32_t)sizeof(NodeBox));
+    else
+        return cboxes[id];
+}
+// the node count below which every 32-bit offset of the NARROW loads is exact
+constexpr uint64_t WALK_NARROW_NODES = (1ull << 32) / sizeof(NodeBox);
+inline bool walk_narrow_ok(uint64_t nnodes) { return nnodes < WALK_NARROW_NODES; }
+
 // One internal node with split axis D (a constant after inlining): true = the walk entered a child (w.node, its box, bounds and
 // wanted mask wm); false = no lane wants either child, the state is dead and
 // the next pop rewrites all of it.
@@ -343,7 +373,7 @@ __device__ __forceinline__ bool walk_step(PacketWalk &w, const int D, const uint
 // advance the walk to the next leaf some lane wants: true = leaf w.node holds
 // the points [lpos, lend); false = the walk is over.  visits counts the node
 // records looked at (the work counter node_visits).
-template <bool M, bool STATS>
+template <bool M, bool STATS, bool NARROW>
 __device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cnodes,
                                                const cbox_ptr cboxes, const float qx,
                                                const float qy, const float qz, const float kth,
@@ -362,8 +392,8 @@ __device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cn
             } else {
                 --w.sp;
                 w.node = (uint32_t)__builtin_amdgcn_readlane((int)w.sk_node, w.sp);
-                const NodeBox nb = cboxes[w.node];
-                const nbkd_node nd = cnodes[w.node];
+                const NodeBox nb = walk_load_box<NARROW>(cboxes, w.node);
+                const nbkd_node nd = walk_load_node<NARROW>(cnodes, w.node);
 #pragma unroll
                 for (int a = 0; a < 6; ++a) w.bx[a] = uni(__float_as_uint(nb.b[a]));
                 dim = (int)uni((uint32_t)nd.dimension);
@@ -392,7 +422,7 @@ __device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cn
                     loaded = walk_step<M>(w, 2, split_bits, left, right, wm, qx, qy, qz, kth, L);
                 // the child's record (asked for also when no child was
                 // entered: no branch, and the pop that follows overwrites it)
-                const nbkd_node nd = cnodes[w.node];
+                const nbkd_node nd = walk_load_node<NARROW>(cnodes, w.node);
                 dim = (int)uni((uint32_t)nd.dimension);
                 split_bits = uni(__float_as_uint(nd.split));
                 left = uni(nd.left);
@@ -401,6 +431,211 @@ __device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cn
         }
     } while (end == RUN);
     return end == LEAF;
+}
+
+// ------------------------------------------------------------------ hand-scheduled descent
+// The descent of the plain-metric walk with 32-bit offsets (96 % of the
+// bench's packets), from a wanted node whose record is loaded down to a leaf
+// or to a node neither of whose children any lane wants: the arithmetic of
+// walk_step<false> instruction for instruction (same operands, same
+// association, so the same bits and the same leaf sequence), with the control
+// flow the compiler does not produce from any C++ form tried
+// (profiles/r08a_walk_static.txt).  The state is where the code stands: the
+// wanted tests are s_cmp_lg_u64 on the two compare masks and branches on SCC,
+// each outcome (left only, right only, both wanted and the vote's two sides)
+// has its own few moves, and nothing is copied on the back edge.  A visit
+// that enters the only wanted child is 8 SALU, 5 to 7 branches, one s_load and
+// 12 VALU (the compiled loop: 28, 7, 1, 16).
+//
+// The record lives in s[68:71] (dimension, split, left, right): an
+// s_load_dwordx4 needs an aligned register quadruple, which an inline-assembly
+// operand cannot name the words of, so the block owns these four registers.
+// They lie inside the 74 SGPRs (80 with VCC and its kin) that the compiler
+// itself keeps a kernel of 8 waves per SIMD under, so the register allocator
+// works around them and the kernel's count cannot pass that bound on their
+// account: it is 78 for the first-pass instance (scripts/asm_counts.py
+// --max-sgprs 80 checks a listing).  Higher numbers do pass it, and cost a
+// wave: owning s[88:91] the kernel counted 98 SGPRs and was 1.9 ms slower
+// than the parent; owning s[76:79] (86, registers the compiler holds back and
+// warns about) 0.4 to 1.0 ms faster, at 7 waves per SIMD by the counters where
+// the compiler reported 8; owning these, 2.2 ms faster (step 50.01 -> 47.78 ms,
+// profiles/r08a_collect_ab.txt, r08a_pmc_sq.txt).  The
+// block reads the node table through the
+// scalar cache only and writes registers only.  Wait states gfx950 wants by hand: two between a VALU write
+// of VCC and the v_cndmask that reads it.
+//
+// in:  dim / split / left / right = the record of w.node, wm = the lanes that
+//      want it (nonzero)
+// out: dim < 0: the walk stands on leaf w.node, left / right = its point range;
+//      dim == 0: no lane wants either child of the last node, the state is dead
+// the per-axis bound arithmetic; tl in %[c], tr in %[b], then the two ballots
+#define NBKD_WD_AXIS(Q, TM, A, B)                                                                  \
+    "v_subrev_f32_e32 %[a], s69, " Q "\n"                                                          \
+    "v_cmp_lt_f32_e32 vcc, 0, %[a]\n"                                                              \
+    "v_mul_f32_e32 %[b], %[a], %[a]\n"                                                             \
+    "s_nop 0\n"                                                                                    \
+    "v_cndmask_b32_e32 %[c], " TM ", %[b], vcc\n"                                                  \
+    "v_cndmask_b32_e32 %[b], %[b], " TM ", vcc\n"                                                  \
+    "v_add_f32_e32 %[a], %[c], " A "\n"                                                            \
+    "v_add_f32_e32 %[d], %[b], " A "\n"                                                            \
+    "v_add_f32_e32 %[a], %[a], " B "\n"                                                            \
+    "v_add_f32_e32 %[d], %[d], " B "\n"                                                            \
+    "v_cmp_le_f32_e64 %[wl], %[a], %[kth]\n"                                                       \
+    "v_cmp_le_f32_e64 %[wr], %[d], %[kth]\n"
+// axis 2: (tm0 + tm1) + t; the sum of the other two terms fills the wait states
+#define NBKD_WD_AXIS2(Q, TM, A, B)                                                                 \
+    "v_subrev_f32_e32 %[a], s69, " Q "\n"                                                          \
+    "v_cmp_lt_f32_e32 vcc, 0, %[a]\n"                                                              \
+    "v_mul_f32_e32 %[b], %[a], %[a]\n"                                                             \
+    "v_add_f32_e32 %[d], " A ", " B "\n"                                                           \
+    "v_cndmask_b32_e32 %[c], " TM ", %[b], vcc\n"                                                  \
+    "v_cndmask_b32_e32 %[b], %[b], " TM ", vcc\n"                                                  \
+    "v_add_f32_e32 %[a], %[d], %[c]\n"                                                             \
+    "v_add_f32_e32 %[d], %[d], %[b]\n"                                                             \
+    "v_cmp_le_f32_e64 %[wl], %[a], %[kth]\n"                                                       \
+    "v_cmp_le_f32_e64 %[wr], %[d], %[kth]\n"
+// which children are wanted; both: the vote, the push of the far child into
+// lane sp of the stack; then the entered child's bound term, mask and id
+#define NBKD_WD_DECIDE(T, Q, TM)                                                                   \
+    "s_cmp_lg_u64 %[wr], 0\n"                                                                      \
+    "s_cbranch_scc0 .Lwd_" T "nr_%=\n"                                                             \
+    "s_cmp_lg_u64 %[wl], 0\n"                                                                      \
+    "s_cbranch_scc0 .Lwd_" T "R_%=\n"                                                              \
+    "v_cmp_lt_f32_e32 vcc, s69, " Q "\n"                                                           \
+    "s_and_b64 vcc, vcc, %[wm]\n"                                                                  \
+    "s_bcnt1_i32_b64 %[s0], vcc\n"                                                                 \
+    "s_bcnt1_i32_b64 %[s1], %[wm]\n"                                                               \
+    "s_lshl_b32 %[s0], %[s0], 1\n"                                                                 \
+    "s_lshl_b64 %[pm], 1, %[sp]\n"                                                                 \
+    "s_add_i32 %[sp], %[sp], 1\n"                                                                  \
+    "s_cmp_gt_u32 %[s0], %[s1]\n"                                                                  \
+    "s_cbranch_scc1 .Lwd_" T "pR_%=\n"                                                             \
+    "v_mov_b32_e32 %[a], s71\n"                                                                    \
+    "v_cndmask_b32_e64 %[sk], %[sk], %[a], %[pm]\n"                                                \
+    ".Lwd_" T "L_%=:\n"                                                                            \
+    "v_mov_b32_e32 " TM ", %[c]\n"                                                                 \
+    "s_mov_b64 %[wm], %[wl]\n"                                                                     \
+    "s_mov_b32 %[nd], s70\n"                                                                       \
+    "s_branch .Lwd_load_%=\n"                                                                      \
+    ".Lwd_" T "nr_%=:\n"                                                                           \
+    "s_cmp_lg_u64 %[wl], 0\n"                                                                      \
+    "s_cbranch_scc1 .Lwd_" T "L_%=\n"                                                              \
+    "s_branch .Lwd_none_%=\n"                                                                      \
+    ".Lwd_" T "pR_%=:\n"                                                                           \
+    "v_mov_b32_e32 %[a], s70\n"                                                                    \
+    "v_cndmask_b32_e64 %[sk], %[sk], %[a], %[pm]\n"                                                \
+    ".Lwd_" T "R_%=:\n"                                                                            \
+    "v_mov_b32_e32 " TM ", %[b]\n"                                                                 \
+    "s_mov_b64 %[wm], %[wr]\n"                                                                     \
+    "s_mov_b32 %[nd], s71\n"
+#define NBKD_WD_BODY(VISIT)                                                                        \
+    "s_mov_b32 s68, %[dim]\n"                                                                      \
+    "s_mov_b32 s69, %[spl]\n"                                                                      \
+    "s_mov_b32 s70, %[lf]\n"                                                                       \
+    "s_mov_b32 s71, %[rt]\n"                                                                       \
+    ".Lwd_top_%=:\n" VISIT                                                                         \
+    "s_cmp_lt_i32 s68, 0\n"                                                                        \
+    "s_cbranch_scc1 .Lwd_leaf_%=\n"                                                                \
+    "s_cmp_eq_u32 s68, 1\n"                                                                        \
+    "s_cbranch_scc1 .Lwd_y_%=\n"                                                                   \
+    "s_cmp_eq_u32 s68, 0\n"                                                                        \
+    "s_cbranch_scc1 .Lwd_x_%=\n"                                                                   \
+    NBKD_WD_AXIS2("%[qz]", "%[tm2]", "%[tm0]", "%[tm1]")                                           \
+    NBKD_WD_DECIDE("z", "%[qz]", "%[tm2]")                                                         \
+    "s_branch .Lwd_load_%=\n"                                                                      \
+    ".Lwd_y_%=:\n"                                                                                 \
+    NBKD_WD_AXIS("%[qy]", "%[tm1]", "%[tm0]", "%[tm2]")                                            \
+    NBKD_WD_DECIDE("y", "%[qy]", "%[tm1]")                                                         \
+    "s_branch .Lwd_load_%=\n"                                                                      \
+    ".Lwd_x_%=:\n"                                                                                 \
+    NBKD_WD_AXIS("%[qx]", "%[tm0]", "%[tm1]", "%[tm2]")                                            \
+    NBKD_WD_DECIDE("x", "%[qx]", "%[tm0]")                                                         \
+    ".Lwd_load_%=:\n"                                                                              \
+    "s_lshl_b32 %[s0], %[nd], 4\n"                                                                 \
+    "s_load_dwordx4 s[68:71], %[base], %[s0] offset:0x0\n"                                         \
+    "s_waitcnt lgkmcnt(0)\n"                                                                       \
+    "s_branch .Lwd_top_%=\n"                                                                       \
+    ".Lwd_none_%=:\n"                                                                              \
+    "s_mov_b32 %[dim], 0\n"                                                                        \
+    "s_branch .Lwd_end_%=\n"                                                                       \
+    ".Lwd_leaf_%=:\n"                                                                              \
+    "s_mov_b32 %[dim], s68\n"                                                                      \
+    "s_mov_b32 %[lf], s70\n"                                                                       \
+    "s_mov_b32 %[rt], s71\n"                                                                       \
+    ".Lwd_end_%=:\n"
+#define NBKD_WD_OPERANDS                                                                           \
+    [dim] "+s"(dim), [lf] "+s"(left), [rt] "+s"(right), [nd] "+s"(w.node), [sp] "+s"(w.sp),        \
+        [wm] "+s"(wm), [tm0] "+v"(w.tm[0]), [tm1] "+v"(w.tm[1]), [tm2] "+v"(w.tm[2]),              \
+        [sk] "+v"(w.sk_node), [a] "=&v"(ta), [b] "=&v"(tb), [c] "=&v"(tc), [d] "=&v"(td),          \
+        [wl] "=&s"(wl), [wr] "=&s"(wr), [pm] "=&s"(pm), [s0] "=&s"(s0), [s1] "=&s"(s1)
+template <bool STATS>
+__device__ __forceinline__ void walk_descend(PacketWalk &w, const cnode_ptr cnodes, uint32_t &dim,
+                                             const uint32_t split_bits, uint32_t &left,
+                                             uint32_t &right, uint64_t wm, const float qx,
+                                             const float qy, const float qz, const float kth,
+                                             uint32_t &visits) {
+    float ta, tb, tc, td;
+    uint64_t wl, wr, pm;
+    uint32_t s0, s1;
+    const uint64_t base = (uint64_t)cnodes;
+    if constexpr (STATS)
+        asm volatile(NBKD_WD_BODY("s_add_u32 %[vis], %[vis], 1\n")
+                     : NBKD_WD_OPERANDS, [vis] "+s"(visits)
+                     : [spl] "s"(split_bits), [base] "s"(base), [qx] "v"(qx), [qy] "v"(qy),
+                       [qz] "v"(qz), [kth] "v"(kth)
+                     : "s68", "s69", "s70", "s71", "vcc", "scc");
+    else
+        asm volatile(NBKD_WD_BODY("")
+                     : NBKD_WD_OPERANDS
+                     : [spl] "s"(split_bits), [base] "s"(base), [qx] "v"(qx), [qy] "v"(qy),
+                       [qz] "v"(qz), [kth] "v"(kth)
+                     : "s68", "s69", "s70", "s71", "vcc", "scc");
+}
+#undef NBKD_WD_OPERANDS
+#undef NBKD_WD_BODY
+#undef NBKD_WD_DECIDE
+#undef NBKD_WD_AXIS2
+#undef NBKD_WD_AXIS
+
+// walk_next_leaf<false, STATS, true> around the hand-scheduled descent: the
+// pop in C++ (every call starts with one), the descent from the popped node
+// in walk_descend; one loop with one exit block
+template <bool STATS>
+__device__ __forceinline__ bool walk_next_leaf_plain(PacketWalk &w, const cnode_ptr cnodes,
+                                                     const cbox_ptr cboxes, const float qx,
+                                                     const float qy, const float qz,
+                                                     const float kth, const float L,
+                                                     uint32_t &lpos, uint32_t &lend,
+                                                     uint32_t &visits) {
+    uint32_t found = 0, dim = 0, left = 0, right = 0;
+    while (w.sp != 0) {
+        --w.sp;
+        w.node = (uint32_t)__builtin_amdgcn_readlane((int)w.sk_node, w.sp);
+        const NodeBox nb = walk_load_box<true>(cboxes, w.node);
+        const nbkd_node nd = walk_load_node<true>(cnodes, w.node);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) w.bx[a] = uni(__float_as_uint(nb.b[a]));
+        // the record is pinned here, before the wanted test, so that its load
+        // is issued beside the box load and one wait covers both
+        dim = uni((uint32_t)nd.dimension);
+        const uint32_t split_bits = uni(__float_as_uint(nd.split));
+        left = uni(nd.left);
+        right = uni(nd.right);
+        w.tm[0] = box_lb_axis<false>(qx, __uint_as_float(w.bx[0]), __uint_as_float(w.bx[1]), L);
+        w.tm[1] = box_lb_axis<false>(qy, __uint_as_float(w.bx[2]), __uint_as_float(w.bx[3]), L);
+        w.tm[2] = box_lb_axis<false>(qz, __uint_as_float(w.bx[4]), __uint_as_float(w.bx[5]), L);
+        const uint64_t wm = __ballot((w.tm[0] + w.tm[1]) + w.tm[2] <= kth);
+        if (wm == 0) continue;
+        walk_descend<STATS>(w, cnodes, dim, split_bits, left, right, wm, qx, qy, qz, kth, visits);
+        if ((int)dim < 0) {
+            asm volatile(""); // keeps this a branch: as a select it costs two lane masks per pop
+            found = 1;
+            break;
+        }
+    }
+    lpos = left;
+    lend = right;
+    return found != 0;
 }
 
 } // namespace dev

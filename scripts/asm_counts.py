@@ -3,7 +3,10 @@
 every loop that pops the wave stack (the packet walk: a v_readlane_b32 with an
 SGPR lane select, which only the pop has), each from its loop header label to
 its last backward branch.
-python scripts/asm_counts.py knn_collect.s 'knn_collect_grp_kernelILb1ELi8ELb0ELb0ELb1E'"""
+python scripts/asm_counts.py knn_collect.s 'knn_collect_grp_kernelILb1ELi8ELb0ELb0ELb1E' [--max-sgprs N]
+--max-sgprs N: exit 1 if the kernel's TotalNumSgprs is above N.  The collect kernel's
+hand-scheduled descent (packet.hpp walk_descend) owns four fixed SGPRs; 80 is what the
+compiler itself keeps a kernel of 8 waves per SIMD under, and a kernel above it loses a wave."""
 import re
 import sys
 
@@ -47,6 +50,7 @@ def counts(lines):
 
 def main():
     path, key = sys.argv[1], sys.argv[2]
+    max_sgprs = int(sys.argv[sys.argv.index("--max-sgprs") + 1]) if "--max-sgprs" in sys.argv else None
     text = open(path).read().splitlines()
     start = next(i for i, ln in enumerate(text) if re.match(r"^_Z\S*" + re.escape(key) + r"\S*:", ln))
     end = next(i for i in range(start, len(text)) if text[i].strip().startswith("s_endpgm"))
@@ -58,6 +62,13 @@ def main():
     print("kernel", text[start].rstrip(":"))
     for m in meta:
         print("  ", m)
+    if max_sgprs is not None:
+        # the first TotalNumSgprs after the kernel's end is its own
+        n = next(int(re.search(r"; TotalNumSgprs: (\d+)", ln).group(1)) for ln in text[end:]
+                 if "; TotalNumSgprs:" in ln)
+        print("   ; TotalNumSgprs:", n)
+        if n > max_sgprs:
+            sys.exit(f"{n} SGPRs, more than {max_sgprs}")
     print("  whole kernel:", dict(sorted(counts(body).items())))
     label = {ln.split(":")[0]: i for i, ln in enumerate(body) if re.match(r"^\.LBB\d+_\d+:", ln)}
     pops = [i for i, ln in enumerate(body) if re.match(r"\s*v_readlane_b32 s\d+, v\d+, s\d+", ln)]
