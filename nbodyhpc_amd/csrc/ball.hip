@@ -53,42 +53,18 @@ __device__ __forceinline__ void ball_fill_walk(const DevTree &t, const uint32_t 
                                                const float qy, const float qz, const float thr,
                                                const uint64_t wpos) {
     const float L = t.box;
-    uint32_t sk_node = 0;
-    int sp = 0;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
-    uint32_t node = 0;
-    float bx[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        bx[2 * a] = PER ? 0.0f : -FLT_MAX;
-        bx[2 * a + 1] = PER ? L : FLT_MAX;
-    }
-    float tm[3] = {box_lb_axis<M>(qx, bx[0], bx[1], L), box_lb_axis<M>(qy, bx[2], bx[3], L),
-                   box_lb_axis<M>(qz, bx[4], bx[5], L)};
-    uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= thr);
-    bool have = wm != 0;
-    nbkd_node nd = cnodes[0]; // record of `node` while `have`
-    // the shared packet walk (packet.hpp: per-axis steps, node-id stack)
-    constexpr bool STATS = false;
-    const float kth = thr;
-    uint32_t st[1] = {0};
-    (void)st;
-    uint32_t cnt = 0;
-    for (;;) {
-        bool found;
-        uint32_t lpos = 0, lend = 0;
-        NBKD_GWALK(found, lpos, lend);
-        if (!found) break;
-        // the leaf's tight box (leafinfo lo.xyz, hi.xyz): one s_load_dwordx8
-        const NodeBox lb_ = ((cbox_ptr)linfo)[node];
-        const float tb[6] = {lb_.b[0], lb_.b[3], lb_.b[1], lb_.b[4], lb_.b[2], lb_.b[5]};
+    PacketWalk w;
+    walk_begin(w);
+    uint32_t cnt = 0, lpos = 0, lend = 0, visits = 0;
+    while (walk_next_leaf<M, false, false>(w, cnodes, cboxes, qx, qy, qz, thr, L, lpos, lend,
+                                           visits)) {
+        float tb[6];
+        leaf_tight_box(linfo, w.node, tb);
         const bool need = box_lb2<M>(qx, qy, qz, tb, L) <= thr;
         if (!__any(need)) continue;
-        // a leaf holding padding points (FLT_MAX, never inside) is always evaluated
-        bool padded = false;
-#pragma unroll
-        for (int j = 0; j < NBKD_PAD_LEAVES; ++j) padded |= pad.id[j] == node;
+        const bool padded = leaf_padded(pad, w.node);
         const bool full = need && !padded && box_ub2<PER>(qx, qy, qz, tb) <= thr;
         const bool part = need && !full;
         for (uint32_t c0 = lpos; c0 < lend; c0 += CHUNK) {
@@ -137,17 +113,9 @@ ball_fill_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__r
     const bool active = valid && inside;
     const float thr = active ? r2 : -INFINITY;
     const uint64_t wpos = active ? row_offsets[qo] : 0;
-    // every active lane's ball clears the box faces by a margin r' > r: the
-    // plain formulas then give the periodic ones' bits for every point within
-    // r and fail the test for every point beyond (knn_collect.hip
-    // collect_packet), so the packet walks and tests with them
+    // every active lane's ball clears the box faces: the plain formulas
     bool plain = false;
-    if constexpr (PER) {
-        const float r1 = sqrtf(fmaxf(r2, 0.0f)) * 1.01f + L * 1e-6f;
-        const bool wf = !active || (r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 &&
-                                    L - qy >= r1 && qz >= r1 && L - qz >= r1);
-        plain = __all(wf);
-    }
+    if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
     if (plain)
         ball_fill_walk<PER, false>(t, linfo, pad, out_idx, W, lane, qx, qy, qz, thr, wpos);
     else
@@ -189,7 +157,11 @@ struct alignas(16) BallLds2 {
 #endif
 };
 
-// one internal node with split axis D for both query sets (NBKD_GSTEP's logic)
+// The two-set walk: the traversal of packet.hpp's walk_step / walk_next_leaf
+// (same bounds, vote, pushes and pop test) for two queries per lane, each set
+// with its own bounds and wanted masks, the vote taken over both.  Local to
+// ball_count2_kernel.
+// one internal node with split axis D for both query sets
 #define NBKD_GSTEP2(D)                                                                             \
     {                                                                                              \
         const float split = nd.split;                                                              \
@@ -533,6 +505,8 @@ ball_count2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *_
 #endif
     bool plain = false;
     if constexpr (PER) {
+        // (ball_clears_faces of packet.hpp written out for both sets: through
+        // the helper this benchmarked kernel compiles to other code)
         const float r1 = sqrtf(fmaxf(r2, 0.0f)) * 1.01f + L * 1e-6f;
         const bool wa = !acta || (r1 <= 0.25f * L && ax >= r1 && L - ax >= r1 && ay >= r1 &&
                                   L - ay >= r1 && az >= r1 && L - az >= r1);
@@ -715,9 +689,7 @@ void launch_ball_packet(const Tree &t, const float *q, const uint32_t *order, ui
         const char *e = knob("NBKD_BALL_PLAIN");
         return !(e && atoi(e) == 0);
     }();
-    PadLeaves pad;
-    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
-        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    const PadLeaves pad = pad_leaves_of(t);
     if (out_idx) { // CSR fill: 64-query packets
         const unsigned blocks = (unsigned)((m + TB - 1) / TB);
         if (t.periodic)

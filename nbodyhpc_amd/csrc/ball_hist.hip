@@ -83,41 +83,20 @@ __device__ __forceinline__ void ball_hist_walk(const DevTree &t, const uint32_t 
                                                const float qx, const float qy, const float qz,
                                                const float kth) {
     const float L = t.box;
-    uint32_t sk_node = 0;
-    int sp = 0;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
-    uint32_t node = 0;
-    float bx[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        bx[2 * a] = PER ? 0.0f : -FLT_MAX;
-        bx[2 * a + 1] = PER ? L : FLT_MAX;
-    }
-    float tm[3] = {box_lb_axis<M>(qx, bx[0], bx[1], L), box_lb_axis<M>(qy, bx[2], bx[3], L),
-                   box_lb_axis<M>(qz, bx[4], bx[5], L)};
-    uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= kth);
-    bool have = wm != 0;
-    nbkd_node nd = cnodes[0]; // record of `node` while `have`
-    // the shared packet walk (packet.hpp: per-axis steps, node-id stack)
-    constexpr bool STATS = false;
-    uint32_t st[1] = {0};
-    (void)st;
-    for (;;) {
-        bool found;
-        uint32_t lpos = 0, lend = 0;
-        NBKD_GWALK(found, lpos, lend);
-        if (!found) break;
-        // the leaf's tight box (leafinfo lo.xyz, hi.xyz): one s_load_dwordx8
-        const NodeBox lb_ = ((cbox_ptr)linfo)[node];
-        const float tb[6] = {lb_.b[0], lb_.b[3], lb_.b[1], lb_.b[4], lb_.b[2], lb_.b[5]};
+    PacketWalk w;
+    walk_begin(w);
+    uint32_t lpos = 0, lend = 0, visits = 0;
+    while (walk_next_leaf<M, false, false>(w, cnodes, cboxes, qx, qy, qz, kth, L, lpos, lend,
+                                           visits)) {
+        float tb[6];
+        leaf_tight_box(linfo, w.node, tb);
         const float lb = box_lb2<M>(qx, qy, qz, tb, L);
         const bool need = lb <= kth;
         if (!__any(need)) continue;
-        // a leaf holding padding points (FLT_MAX, in no bin) is always evaluated
-        bool padded = false;
-#pragma unroll
-        for (int j = 0; j < NBKD_PAD_LEAVES; ++j) padded |= pad.id[j] == node;
+        // (a leaf holding padding points, in no bin, is always evaluated)
+        const bool padded = leaf_padded(pad, w.node);
         const float ub = box_ub2<PER>(qx, qy, qz, tb);
         // jall: the thresholds below lb (the bin of a leaf no threshold splits);
         // tmask: the thresholds that may split the leaf for some lane; base:
@@ -181,16 +160,10 @@ ball_hist_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__r
     const bool active = valid && inside;
     const float r2 = unif(thr[nr - 1]);
     const float kth = active ? r2 : -INFINITY;
-    // every active lane's ball of the largest radius clears the box faces by
-    // a margin: the packet walks and tests with the plain formulas (ball.hip
-    // ball_fill_kernel)
+    // every active lane's ball of the largest radius clears the box faces:
+    // the plain formulas
     bool plain = false;
-    if constexpr (PER) {
-        const float r1 = sqrtf(fmaxf(r2, 0.0f)) * 1.01f + L * 1e-6f;
-        const bool wf = !active || (r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 &&
-                                    L - qy >= r1 && qz >= r1 && L - qz >= r1);
-        plain = __all(wf);
-    }
+    if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
     if (plain)
         ball_hist_walk<PER, false>(t, linfo, pad, p4s, hist, thr, nr, lane, qx, qy, qz, kth);
     else
@@ -267,9 +240,7 @@ hist_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *__
 void launch_ball_hist(const Tree &t, const float *q, const uint32_t *order, uint32_t m,
                       const HistThr &thr, int nr, uint32_t *out_counts,
                       unsigned long long *totals, hipStream_t s) {
-    PadLeaves pad;
-    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
-        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    const PadLeaves pad = pad_leaves_of(t);
     const unsigned blocks = (unsigned)(((uint64_t)m + TB - 1) / TB);
     const size_t lds = (size_t)WPB * hist_wave_bytes(nr);
     if (t.periodic)

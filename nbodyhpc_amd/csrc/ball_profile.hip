@@ -6,8 +6,8 @@
 // lane's own thresholds, with ball_sum.hip's staged values where the histogram
 // counts.
 //
-// ball_profile_kernel: 64-query packets, one wave each, the shared packet walk
-// (packet.hpp) with the lane's own bound t_i,nr-1.  Per wave in LDS: the staged
+// ball_profile_kernel: 64-query packets, one wave each, the packet walk
+// (packet.hpp, the macro form NBKD_GWALK) with the lane's own bound t_i,nr-1.  Per wave in LDS: the staged
 // chunk of Tree::p4, its rows of the values in tree order (vt, written once per
 // call by launch_ball_sum_gather), acc[(nr + 1)][NV][64] and thr[nr][64].  Lane
 // l owns column l of every row of acc and thr (64 four-byte banks: the wave's
@@ -168,7 +168,8 @@ __device__ __forceinline__ void ball_profile_walk(const DevTree &t,
     uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= kth);
     bool have = wm != 0;
     nbkd_node nd = cnodes[0]; // record of `node` while `have`
-    // the shared packet walk (packet.hpp), its bound each lane's own kth
+    // the packet walk in its macro form (packet.hpp says why this kernel keeps
+    // it), its bound each lane's own kth
     constexpr bool STATS = false;
     uint32_t st[1] = {0};
     (void)st;
@@ -389,9 +390,7 @@ void launch_ball_profile(const Tree &t, const float *q, const float *scale, cons
                          uint32_t m, const ProfRadii &R, int nr, const float *vt, int nv,
                          float *out_sum, hipStream_t s) {
     if (m == 0) return;
-    PadLeaves pad;
-    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
-        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    const PadLeaves pad = pad_leaves_of(t);
     switch (nv) {
     case 1: launch_profile_n<1>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;
     case 2: launch_profile_n<2>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;

@@ -86,46 +86,24 @@ __device__ __forceinline__ void ball_sum_walk(const DevTree &t, const uint32_t *
                                               const float qy, const float qz, const float thr,
                                               const float inv, float (&acc)[NV], uint32_t &cnt) {
     const float L = t.box;
-    uint32_t sk_node = 0;
-    int sp = 0;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
-    uint32_t node = 0;
-    float bx[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        bx[2 * a] = PER ? 0.0f : -FLT_MAX;
-        bx[2 * a + 1] = PER ? L : FLT_MAX;
-    }
-    float tm[3] = {box_lb_axis<M>(qx, bx[0], bx[1], L), box_lb_axis<M>(qy, bx[2], bx[3], L),
-                   box_lb_axis<M>(qz, bx[4], bx[5], L)};
-    uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= thr);
-    bool have = wm != 0;
-    nbkd_node nd = cnodes[0]; // record of `node` while `have`
-    // the shared packet walk (packet.hpp), its bound each lane's own thr
-    constexpr bool STATS = false;
-    const float kth = thr;
-    uint32_t st[1] = {0};
-    (void)st;
-    for (;;) {
-        bool found;
-        uint32_t lpos = 0, lend = 0;
-        NBKD_GWALK(found, lpos, lend);
-        if (!found) break;
-        const NodeBox lb_ = ((cbox_ptr)linfo)[node];
-        const float tb[6] = {lb_.b[0], lb_.b[3], lb_.b[1], lb_.b[4], lb_.b[2], lb_.b[5]};
+    // the packet walk (packet.hpp), its bound each lane's own thr
+    PacketWalk w;
+    walk_begin(w);
+    uint32_t lpos = 0, lend = 0, visits = 0;
+    while (walk_next_leaf<M, false, false>(w, cnodes, cboxes, qx, qy, qz, thr, L, lpos, lend,
+                                           visits)) {
+        float tb[6];
+        leaf_tight_box(linfo, w.node, tb);
         const bool need = box_lb2<M>(qx, qy, qz, tb, L) <= thr;
         if (!__any(need)) continue;
         // top-hat only: a lane whose ball contains the leaf's tight box adds
         // the leaf's values without the d2 test (never a leaf with padding
         // points); for the other kernels every point's d2 is needed anyway
         bool full = false;
-        if constexpr (KERN == NBKD_KERNEL_TOPHAT) {
-            bool padded = false;
-#pragma unroll
-            for (int j = 0; j < NBKD_PAD_LEAVES; ++j) padded |= pad.id[j] == node;
-            full = need && !padded && box_ub2<PER>(qx, qy, qz, tb) <= thr;
-        }
+        if constexpr (KERN == NBKD_KERNEL_TOPHAT)
+            full = need && !leaf_padded(pad, w.node) && box_ub2<PER>(qx, qy, qz, tb) <= thr;
         const bool part = need && !full;
         for (uint32_t c0 = lpos; c0 < lend; c0 += CHUNK) {
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
@@ -190,17 +168,10 @@ ball_sum_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__re
         !PER || (qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f && qz <= L);
     const float thr = ball_thr(hq, valid && inside);
     const float inv = ball_inv(hq);
-    // every lane's own ball clears the box faces by a margin r' > h_i (an
-    // empty ball clears them too): the plain formulas then give the periodic
-    // ones' bits for every point within h_i and fail the test for every point
-    // beyond (ball.hip ball_fill_kernel), so the packet walks and tests with them
+    // every lane's own ball clears the box faces (an empty ball clears them
+    // too): the plain formulas
     bool plain = false;
-    if constexpr (PER) {
-        const float r1 = sqrtf(fmaxf(thr, 0.0f)) * 1.01f + L * 1e-6f;
-        const bool wf = thr < 0.0f || (r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 &&
-                                       L - qy >= r1 && qz >= r1 && L - qz >= r1);
-        plain = __all(wf);
-    }
+    if constexpr (PER) plain = __all(thr < 0.0f || ball_clears_faces(thr, qx, qy, qz, L));
     float acc[NV];
 #pragma unroll
     for (int c = 0; c < NV; ++c) acc[c] = 0.0f;
@@ -329,9 +300,7 @@ void launch_ball_sum(const Tree &t, const float *q, const float *h, const uint32
                      uint32_t m, const float *vt, int nv, int kernel, float *out_sum,
                      uint32_t *out_count, hipStream_t s) {
     if (m == 0) return;
-    PadLeaves pad;
-    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
-        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    const PadLeaves pad = pad_leaves_of(t);
     if (kernel == NBKD_KERNEL_TOPHAT)
         launch_sum_k<NBKD_KERNEL_TOPHAT>(t, q, h, order, m, pad, vt, nv, out_sum, out_count, s);
     else if (kernel == NBKD_KERNEL_CUBIC)

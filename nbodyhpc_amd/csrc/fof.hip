@@ -122,43 +122,20 @@ __device__ __forceinline__ void fof_hook_walk(const DevTree &t, const uint32_t *
                                               const int lane, const uint32_t gq, const float qx,
                                               const float qy, const float qz, const float thr) {
     const float L = t.box;
-    uint32_t sk_node = 0;
-    int sp = 0;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
-    uint32_t node = 0;
-    float bx[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        bx[2 * a] = PER ? 0.0f : -FLT_MAX;
-        bx[2 * a + 1] = PER ? L : FLT_MAX;
-    }
-    float tm[3] = {box_lb_axis<M>(qx, bx[0], bx[1], L), box_lb_axis<M>(qy, bx[2], bx[3], L),
-                   box_lb_axis<M>(qz, bx[4], bx[5], L)};
-    uint64_t wm = __ballot((tm[0] + tm[1]) + tm[2] <= thr);
-    bool have = wm != 0;
-    nbkd_node nd = cnodes[0]; // record of `node` while `have`
-    // the shared packet walk (packet.hpp: per-axis steps, node-id stack)
-    constexpr bool STATS = false;
-    const float kth = thr;
-    uint32_t st[1] = {0};
-    (void)st;
     uint32_t rq = gq; // a member of the lane's set: the smallest root it has seen
-    for (;;) {
-        bool found;
-        uint32_t lpos = 0, lend = 0;
-        NBKD_GWALK(found, lpos, lend);
-        if (!found) break;
-        // the leaf's tight box (leafinfo lo.xyz, hi.xyz): one s_load_dwordx8
-        const NodeBox lb_ = ((cbox_ptr)linfo)[node];
-        const float tb[6] = {lb_.b[0], lb_.b[3], lb_.b[1], lb_.b[4], lb_.b[2], lb_.b[5]};
+    PacketWalk w;
+    walk_begin(w);
+    uint32_t lpos = 0, lend = 0, visits = 0;
+    while (walk_next_leaf<M, false, false>(w, cnodes, cboxes, qx, qy, qz, thr, L, lpos, lend,
+                                           visits)) {
+        float tb[6];
+        leaf_tight_box(linfo, w.node, tb);
         // a leaf that starts at or after the lane's own position holds no j < gq
         const bool need = lpos < gq && box_lb2<M>(qx, qy, qz, tb, L) <= thr;
         if (!__any(need)) continue;
-        // a leaf holding padding points (FLT_MAX, never inside) is always evaluated
-        bool padded = false;
-#pragma unroll
-        for (int j = 0; j < NBKD_PAD_LEAVES; ++j) padded |= pad.id[j] == node;
+        const bool padded = leaf_padded(pad, w.node);
         const bool full = need && !padded && box_ub2<PER>(qx, qy, qz, tb) <= thr;
         const bool part = need && !full;
         // whole-leaf lanes need no coordinates: a leaf only they need is not staged
@@ -209,16 +186,9 @@ fof_hook_kernel(DevTree t, const uint32_t *__restrict__ linfo, const uint32_t *_
     }
     const float L = t.box;
     const float thr = active ? b2 : -INFINITY;
-    // every active lane's ball clears the box faces by a margin b' > b: the
-    // plain formulas then give the periodic ones' bits for every point within
-    // b and fail the test for every point beyond (ball.hip ball_fill_kernel)
+    // every active lane's ball clears the box faces: the plain formulas
     bool plain = false;
-    if constexpr (PER) {
-        const float r1 = sqrtf(fmaxf(b2, 0.0f)) * 1.01f + L * 1e-6f;
-        const bool wf = !active || (r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 &&
-                                    L - qy >= r1 && qz >= r1 && L - qz >= r1);
-        plain = __all(wf);
-    }
+    if constexpr (PER) plain = __all(!active || ball_clears_faces(b2, qx, qy, qz, L));
     if (plain)
         fof_hook_walk<PER, false, HV>(t, linfo, pad, parent, W, lane, gq, qx, qy, qz, thr);
     else
@@ -332,9 +302,7 @@ nbkd_status fof(const Tree &t, float b, uint32_t *out_label, uint32_t *out_size,
     // the build permutation (tree position -> input row): labels are input
     // rows also on a tree whose ids nbkd_set_ids replaced
     const uint32_t *perm = t.sidx ? t.sidx : t.idx;
-    PadLeaves pad;
-    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
-        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    const PadLeaves pad = pad_leaves_of(t);
     const unsigned blocks = (unsigned)((t.n8 + TB - 1) / TB);
     fof_init_kernel<<<blocks, TB, 0, s>>>(n8, parent, minid);
     {

@@ -1,6 +1,10 @@
-// Device helpers shared by the packet kernels (knn_collect.hip, ball.hip):
-// direct-to-LDS loads, wave-local sync, the scalar-cache
-// view of the node table, LDS-staged row stores and the fallback listing.
+// Device helpers shared by the packet kernels (knn_collect.hip, ball.hip,
+// ball_hist.hip, ball_sum.hip, ball_profile.hip, fof.hip): direct-to-LDS loads,
+// wave-local sync, the scalar-cache view of the node table, LDS-staged row
+// stores and the fallback listing, the per-leaf idioms of the radius kernels
+// (tight box, padding leaves, the plain-packet test), and the packet walk
+// (walk_begin / walk_next_leaf; the kNN collect's hand-scheduled descent; the
+// macro form ball_profile.hip keeps).
 #pragma once
 
 #include "metric.hpp"
@@ -108,15 +112,35 @@ __device__ __forceinline__ void knn_fail_check(bool valid, bool seeded, uint32_t
 struct PadLeaves {
     uint32_t id[NBKD_PAD_LEAVES];
 };
+// (a tree with more padded leaves than the list holds passes none)
+inline PadLeaves pad_leaves_of(const Tree &t) {
+    PadLeaves pad;
+    for (int j = 0; j < NBKD_PAD_LEAVES; ++j)
+        pad.id[j] = t.npad_leaves <= NBKD_PAD_LEAVES ? t.pad_leaves[j] : 0xFFFFFFFFu;
+    return pad;
+}
+// leaf `node` holds padding points (FLT_MAX, inside no ball): always evaluated
+__device__ __forceinline__ bool leaf_padded(const PadLeaves &pad, const uint32_t node) {
+    bool padded = false;
+#pragma unroll
+    for (int j = 0; j < NBKD_PAD_LEAVES; ++j) padded |= pad.id[j] == node;
+    return padded;
+}
+
+// The lane's ball of squared radius r2 clears the faces of the periodic box
+// by a margin r' > r.  When that holds for every lane that walks, the plain
+// formulas give the periodic ones' bits for every point within r and fail the
+// test for every point beyond (knn_collect.hip collect_packet), so the packet
+// walks and tests with them.  The caller adds its own guard for the lanes that
+// do not walk, and the vote.
+__device__ __forceinline__ bool ball_clears_faces(const float r2, const float qx, const float qy,
+                                                  const float qz, const float L) {
+    const float r1 = sqrtf(fmaxf(r2, 0.0f)) * 1.01f + L * 1e-6f;
+    return r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 && L - qy >= r1 && qz >= r1 &&
+           L - qz >= r1;
+}
 
 // ------------------------------------------------------------------ packet walk
-// The wave's depth-first walk as macros (ball.hip, ball_hist.hip, ball_sum.hip,
-// ball_profile.hip, fof.hip; the kNN collect uses the scalar-resident form of
-// the same traversal further down, walk_next_leaf).  The macros expect in
-// scope: lane, qx/qy/qz, the bound kth, L, cnodes, the walk state node / nd (its
-// record while `have`) / have / wm / bx[6] / tm[3], the wave stack sp / sk_node,
-// the cell boxes cboxes, the metric switch M and STATS / st (node visits in
-// st[0]).
 // v = lanes in `mask` ? val : old, as one v_cndmask (a select of a uniform
 // value into one lane otherwise compiles to exec-masked branches)
 __device__ __forceinline__ float lane_set(float old, float val, uint64_t mask) {
@@ -133,11 +157,12 @@ __device__ __forceinline__ uint32_t lane_set(uint32_t old, uint32_t val, uint64_
 // The wave stack holds node ids only: a pushed far child's id in lane sp of
 // sk_node.  A popped node's box is read back from the tree's per-node cell
 // boxes (Tree::nbox: the root box cut by the splits on the node's path, the
-// values bx held when it was pushed), one s_load_dwordx8 beside the node
-// record.  Round 2 kept the box in six more stack VGPRs (six selects per push,
-// six readlanes per pop): collect 50.03 -> 48.80 ms, radius count 126.1 ->
-// 121.8 ms at 1e8, same output SHA (profiles/r03_ab7_node_stack.txt); the
-// collect kernel needs 58 VGPRs instead of 64.
+// values the walk's box held when the node was pushed), one s_load_dwordx8
+// beside the node record.  Round 2 kept the box in six more stack VGPRs (six
+// selects per push, six readlanes per pop): collect 50.03 -> 48.80 ms, radius
+// count 126.1 -> 121.8 ms at 1e8, same output SHA
+// (profiles/r03_ab7_node_stack.txt); the collect kernel needs 58 VGPRs instead
+// of 64.
 struct NodeBox {
     float b[8];
 };
@@ -147,6 +172,37 @@ typedef const __attribute__((address_space(4))) NodeBox *cbox_ptr;
 typedef const NodeBox *cbox_ptr;
 #endif
 
+// the tight box of leaf `node` (leafinfo lo.xyz, hi.xyz: one s_load_dwordx8)
+// as lo.x, hi.x, lo.y, hi.y, lo.z, hi.z
+__device__ __forceinline__ void leaf_tight_box(const uint32_t *__restrict__ linfo,
+                                               const uint32_t node, float (&tb)[6]) {
+    const NodeBox lb = ((cbox_ptr)linfo)[node];
+    tb[0] = lb.b[0];
+    tb[1] = lb.b[3];
+    tb[2] = lb.b[1];
+    tb[3] = lb.b[4];
+    tb[4] = lb.b[2];
+    tb[5] = lb.b[5];
+}
+
+// The wave's depth-first walk over a packet of 64 queries, one per lane, each
+// with its own bound kth (knn_collect.hip, ball.hip's CSR fill, ball_hist.hip,
+// ball_sum.hip, fof.hip):
+//     PacketWalk w;
+//     walk_begin(w);
+//     while (walk_next_leaf<M, STATS, NARROW>(w, cnodes, cboxes, qx, qy, qz, kth, L,
+//                                             lpos, lend, visits)) {
+//         ... leaf w.node holds the points [lpos, lend) ...
+//     }
+// At an internal node (walk_step, split axis D a compile-time constant) both
+// children are tested for every lane; a single wanted child is entered, and
+// only when both are wanted the lanes vote which one is near (entered) and
+// which far (pushed).  The walk branches on the node's axis, so no per-lane
+// selects pick the axis.  Against the form that voted and ran the push's
+// selects at every node: collect 51.96 -> 49.4 ms at 1e8 with knn_collect's
+// clamped stores (profiles/r03_ab1_collect_variants.txt,
+// r03_ab3_lazy_vote.txt), radius count 129.0 -> 126.1 ms (r03_ab2_push_ball.txt).
+//
 // Tried and dropped (r04s): 64-B node blocks (a node's record and its
 // children's) so a descent waits on one scalar load per two levels: collect
 // 46.7 -> 50.1 ms, radius count 112.3 -> 124.5 ms at 1e8
@@ -154,94 +210,7 @@ typedef const NodeBox *cbox_ptr;
 // cache; four times the bytes per record and 12 more live SGPRs (spilled
 // kernel arguments) cost more than the shorter chains save.
 //
-// one internal node with split axis D (compile-time): test both children for
-// every lane; a single wanted child is entered, and only when both are wanted
-// the lanes vote which one is near (entered) and which far (pushed, its seven
-// selects under a uniform branch).  The walk branches on the node's axis, so
-// no per-lane selects pick the axis.  Against the form that voted and ran the
-// push's selects at every node: collect 51.96 -> 49.4 ms at 1e8 with
-// knn_collect's clamped stores (profiles/r03_ab1_collect_variants.txt,
-// r03_ab3_lazy_vote.txt), radius count 129.0 -> 126.1 ms (r03_ab2_push_ball.txt).
-#define NBKD_GSTEP(D)                                                                              \
-    {                                                                                              \
-        const float split = nd.split;                                                              \
-        const float qd = (D) == 0 ? qx : ((D) == 1 ? qy : qz);                                     \
-        float tl, tr;                                                                              \
-        if constexpr (M) {                                                                         \
-            tl = box_lb_axis<M>(qd, bx[2 * (D)], split, L);                                        \
-            tr = box_lb_axis<M>(qd, split, bx[2 * (D) + 1], L);                                    \
-        } else {                                                                                   \
-            /* plain: the child on q's side keeps the slab's bound tm[D] (the   */                 \
-            /* same bits box_lb_axis gives), the other one is (q - split)^2    */                 \
-            const float dd_ = qd - split;                                                          \
-            const float m2_ = dd_ * dd_;                                                           \
-            tl = dd_ > 0.0f ? m2_ : tm[D];                                                         \
-            tr = dd_ > 0.0f ? tm[D] : m2_;                                                         \
-        }                                                                                          \
-        const float dl = (((D) == 0 ? tl : tm[0]) + ((D) == 1 ? tl : tm[1])) + ((D) == 2 ? tl : tm[2]); \
-        const float dr = (((D) == 0 ? tr : tm[0]) + ((D) == 1 ? tr : tm[1])) + ((D) == 2 ? tr : tm[2]); \
-        const uint64_t wl = __ballot(dl <= kth), wr = __ballot(dr <= kth);                         \
-        bool go_right = wr != 0;                                                                   \
-        if (wl != 0 && wr != 0) {                                                                  \
-            const uint32_t right_votes = (uint32_t)__popcll(wm & __ballot(qd > split));            \
-            const bool right_first = 2 * right_votes > (uint32_t)__popcll(wm);                     \
-            const uint64_t pmask = 1ull << sp;                                                     \
-            sk_node = lane_set(sk_node, right_first ? nd.left : nd.right, pmask);                  \
-            ++sp;                                                                                  \
-            go_right = right_first;                                                                \
-        } else if (wl == 0 && wr == 0) {                                                           \
-            continue;                                                                              \
-        }                                                                                          \
-        node = go_right ? nd.right : nd.left;                                                      \
-        nd = cnodes[node];                                                                         \
-        tm[D] = go_right ? tr : tl;                                                                \
-        if (go_right)                                                                              \
-            bx[2 * (D)] = unif(split);                                                             \
-        else                                                                                       \
-            bx[2 * (D) + 1] = unif(split);                                                         \
-        wm = go_right ? wr : wl;                                                                   \
-        have = true;                                                                               \
-    }
-
-// advance the packet walk to the next leaf some lane wants (FOUND = false: done)
-#define NBKD_GWALK(FOUND, LPOS, LEND)                                                              \
-    FOUND = false;                                                                                 \
-    for (;;) {                                                                                     \
-        if (!have) {                                                                               \
-            if (sp == 0) break;                                                                    \
-            --sp;                                                                                  \
-            node = (uint32_t)__builtin_amdgcn_readlane((int)sk_node, sp);                          \
-            {                                                                                      \
-                const NodeBox nb_ = cboxes[node];                                                  \
-                _Pragma("unroll") for (int a = 0; a < 6; ++a) bx[a] = nb_.b[a];                    \
-            }                                                                                      \
-            tm[0] = box_lb_axis<M>(qx, bx[0], bx[1], L);                                           \
-            tm[1] = box_lb_axis<M>(qy, bx[2], bx[3], L);                                           \
-            tm[2] = box_lb_axis<M>(qz, bx[4], bx[5], L);                                           \
-            wm = __ballot((tm[0] + tm[1]) + tm[2] <= kth);                                         \
-            if (wm == 0) continue;                                                                 \
-            nd = cnodes[node];                                                                     \
-        }                                                                                          \
-        have = false;                                                                              \
-        if constexpr (STATS) ++st[0];                                                              \
-        if (nd.dimension < 0) {                                                                    \
-            LPOS = nd.left;                                                                        \
-            LEND = nd.right;                                                                       \
-            FOUND = true;                                                                          \
-            break;                                                                                 \
-        }                                                                                          \
-        if (nd.dimension == 0)                                                                     \
-            NBKD_GSTEP(0)                                                                          \
-        else if (nd.dimension == 1)                                                                \
-            NBKD_GSTEP(1)                                                                          \
-        else                                                                                       \
-            NBKD_GSTEP(2)                                                                          \
-    }
-
-// ------------------------------------------------------------------ scalar-resident walk
-// The same traversal as NBKD_GWALK / NBKD_GSTEP (same bound arithmetic in the
-// same order, same near-first vote, same pushes and pop tests, so the same
-// leaf sequence), for the kNN collect, in a form the compiler keeps scalar:
+// The form is one the compiler keeps scalar:
 //   - the node record's four words, the popped id and the popped box are
 //     pinned to SGPRs where they are loaded (readfirstlane of a value that is
 //     uniform already costs nothing), and the box is kept as bit patterns:
@@ -249,16 +218,19 @@ typedef const NodeBox *cbox_ptr;
 //     v_cndmask that drags the whole box into VGPRs.  The leaf test and the
 //     axis dispatch are s_cmp on SGPRs, the split a scalar VALU operand;
 //   - one loop with one exit.  The compiler gives every loop with several
-//     exits (a return or break out of a nested step, the FOUND protocol) a
-//     guard variable and re-dispatches on it after the loop, and carries the
-//     `have` flag as a 64-bit lane mask from block to block.  Here the state
-//     is explicit and scalar: the node, whether its record is loaded, and
-//     the stack pointer; an iteration pops (when no record is loaded) and
-//     then looks at one record, and ends in exactly one of enter child, pop,
-//     leaf found, done;
+//     exits (a return or break out of a nested step, a found flag) a guard
+//     variable and re-dispatches on it after the loop, and carries a
+//     "record loaded" flag as a 64-bit lane mask from block to block (the
+//     macro walk this replaced did both: collect step 52.83 -> 51.29 ms,
+//     profiles/r07a_walk_ab.txt; CSR fill, histogram and sums 2 to 14 %
+//     faster, FoF hook 11 to 12 %, profiles/r09a_walk_port_ab.txt).  Here
+//     the state is explicit and scalar: the node, whether its record is
+//     loaded, and the stack pointer; an iteration pops (when no record is
+//     loaded) and then looks at one record, and ends in exactly one of enter
+//     child, pop, leaf found, done;
 //   - every call starts with a pop: the root is pushed before the first call
-//     (walk_begin), and its cell box cboxes[0] is the root box the macro form
-//     starts from, so its bounds and wanted mask have the same bits;
+//     (walk_begin), and its cell box cboxes[0] is the root box ([0, L]^3
+//     periodic, [-FLT_MAX, FLT_MAX]^3 otherwise);
 //   - a pop issues the node's record load beside its box load, one wait for
 //     both (for a popped node no lane wants any more that is 16 B of scalar
 //     cache traffic for nothing; the record is not looked at).
@@ -266,8 +238,13 @@ typedef const NodeBox *cbox_ptr;
 // with a compile-time axis.  Tried and dropped: one body whose split-axis
 // coordinate, box faces and bound term are picked by scalar-controlled
 // selects (10 branches and 42 VALU in the plain walk loop instead of 21 and
-// 70): step 52.61 ms against 51.29 with three bodies and 52.83 for the macro
-// walk, same rows (profiles/r07a_walk_ab.txt).
+// 70): step 52.61 ms against 51.29 with three bodies, same rows
+// (profiles/r07a_walk_ab.txt).
+//
+// Two other walks remain.  ball_count2_kernel's is local to ball.hip: packets
+// of 128 queries, two per lane, with two bound sets and a joint vote
+// (NBKD_GWALK2).  ball_profile.hip still runs the macro form of this walk
+// (NBKD_GWALK, further down, which says why).
 
 struct PacketWalk {
     uint32_t node;    // the node the walk stands on (after a found leaf: its id)
@@ -432,6 +409,93 @@ __device__ __forceinline__ bool walk_next_leaf(PacketWalk &w, const cnode_ptr cn
     } while (end == RUN);
     return end == LEAF;
 }
+
+// ------------------------------------------------------------------ macro walk (ball_profile.hip only)
+// The form walk_next_leaf replaced, kept for ball_profile_walk alone: on the
+// function walk its four-channel instance ran 48.88 ms at 1e7 points against
+// 48.74 with these macros, whose own spread over five runs is 0.11 ms (the
+// other instances were 1.2 to 2 % faster), and the listing (fewer
+// instructions of every class, 75 -> 71 VGPRs) does not explain it
+// (profiles/r09a_walk_port_ab.txt).  The same
+// traversal as walk_step / walk_next_leaf.  The macros expect in scope: lane,
+// qx/qy/qz, the bound kth, L, cnodes, the walk state node / nd (its record
+// while `have`) / have / wm / bx[6] / tm[3], the wave stack sp / sk_node, the
+// cell boxes cboxes, the metric switch M and STATS / st (node visits in st[0]).
+#define NBKD_GSTEP(D)                                                                              \
+    {                                                                                              \
+        const float split = nd.split;                                                              \
+        const float qd = (D) == 0 ? qx : ((D) == 1 ? qy : qz);                                     \
+        float tl, tr;                                                                              \
+        if constexpr (M) {                                                                         \
+            tl = box_lb_axis<M>(qd, bx[2 * (D)], split, L);                                        \
+            tr = box_lb_axis<M>(qd, split, bx[2 * (D) + 1], L);                                    \
+        } else {                                                                                   \
+            /* plain: the child on q's side keeps the slab's bound tm[D] (the   */                 \
+            /* same bits box_lb_axis gives), the other one is (q - split)^2    */                 \
+            const float dd_ = qd - split;                                                          \
+            const float m2_ = dd_ * dd_;                                                           \
+            tl = dd_ > 0.0f ? m2_ : tm[D];                                                         \
+            tr = dd_ > 0.0f ? tm[D] : m2_;                                                         \
+        }                                                                                          \
+        const float dl = (((D) == 0 ? tl : tm[0]) + ((D) == 1 ? tl : tm[1])) + ((D) == 2 ? tl : tm[2]); \
+        const float dr = (((D) == 0 ? tr : tm[0]) + ((D) == 1 ? tr : tm[1])) + ((D) == 2 ? tr : tm[2]); \
+        const uint64_t wl = __ballot(dl <= kth), wr = __ballot(dr <= kth);                         \
+        bool go_right = wr != 0;                                                                   \
+        if (wl != 0 && wr != 0) {                                                                  \
+            const uint32_t right_votes = (uint32_t)__popcll(wm & __ballot(qd > split));            \
+            const bool right_first = 2 * right_votes > (uint32_t)__popcll(wm);                     \
+            const uint64_t pmask = 1ull << sp;                                                     \
+            sk_node = lane_set(sk_node, right_first ? nd.left : nd.right, pmask);                  \
+            ++sp;                                                                                  \
+            go_right = right_first;                                                                \
+        } else if (wl == 0 && wr == 0) {                                                           \
+            continue;                                                                              \
+        }                                                                                          \
+        node = go_right ? nd.right : nd.left;                                                      \
+        nd = cnodes[node];                                                                         \
+        tm[D] = go_right ? tr : tl;                                                                \
+        if (go_right)                                                                              \
+            bx[2 * (D)] = unif(split);                                                             \
+        else                                                                                       \
+            bx[2 * (D) + 1] = unif(split);                                                         \
+        wm = go_right ? wr : wl;                                                                   \
+        have = true;                                                                               \
+    }
+
+// advance the packet walk to the next leaf some lane wants (FOUND = false: done)
+#define NBKD_GWALK(FOUND, LPOS, LEND)                                                              \
+    FOUND = false;                                                                                 \
+    for (;;) {                                                                                     \
+        if (!have) {                                                                               \
+            if (sp == 0) break;                                                                    \
+            --sp;                                                                                  \
+            node = (uint32_t)__builtin_amdgcn_readlane((int)sk_node, sp);                          \
+            {                                                                                      \
+                const NodeBox nb_ = cboxes[node];                                                  \
+                _Pragma("unroll") for (int a = 0; a < 6; ++a) bx[a] = nb_.b[a];                    \
+            }                                                                                      \
+            tm[0] = box_lb_axis<M>(qx, bx[0], bx[1], L);                                           \
+            tm[1] = box_lb_axis<M>(qy, bx[2], bx[3], L);                                           \
+            tm[2] = box_lb_axis<M>(qz, bx[4], bx[5], L);                                           \
+            wm = __ballot((tm[0] + tm[1]) + tm[2] <= kth);                                         \
+            if (wm == 0) continue;                                                                 \
+            nd = cnodes[node];                                                                     \
+        }                                                                                          \
+        have = false;                                                                              \
+        if constexpr (STATS) ++st[0];                                                              \
+        if (nd.dimension < 0) {                                                                    \
+            LPOS = nd.left;                                                                        \
+            LEND = nd.right;                                                                       \
+            FOUND = true;                                                                          \
+            break;                                                                                 \
+        }                                                                                          \
+        if (nd.dimension == 0)                                                                     \
+            NBKD_GSTEP(0)                                                                          \
+        else if (nd.dimension == 1)                                                                \
+            NBKD_GSTEP(1)                                                                          \
+        else                                                                                       \
+            NBKD_GSTEP(2)                                                                          \
+    }
 
 // ------------------------------------------------------------------ hand-scheduled descent
 // The descent of the plain-metric walk with 32-bit offsets (96 % of the

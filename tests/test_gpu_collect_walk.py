@@ -3,7 +3,7 @@ grp_packet) on the smallest shapes at which it can go wrong.  Every case goes
 through the C ABI and is compared with the oracle, distances bit for bit
 (tests.parity.assert_knn_equal).  The last test pins the traversal itself: six
 work counters of the collect pass must equal the values recorded from the
-macro walk (NBKD_GWALK) that this walk replaced, on the same seeded inputs
+macro walk that this walk replaced, on the same seeded inputs
 (tests/golden/collect_walk_counters.json): a walk that visits one node more
 or fewer has changed."""
 import json
