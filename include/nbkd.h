@@ -661,12 +661,29 @@ void nbkd_free(nbkd_tree *tree);
  *                      the table bases wherever every offset fits (fewer than
  *                      2^27 nodes); 1: always through 64-bit addresses, the
  *                      instance larger trees take.  Results never depend on it.
+ *   "collect_one_chunk" 1 (default): a tree with leaf size <= 64 takes the
+ *                      collect kernel's one-chunk instance (no chunk loop, no
+ *                      half-leaf boxes, staging loads at 32-bit offsets where
+ *                      they fit); 0: the general instance that larger leaves
+ *                      take.  Results never depend on it.
  * NEW (no reference counterpart: kdtree/src/cpp/pybind.cpp:196-216 has no knobs). */
 nbkd_status nbkd_set_tuning(const char *name, double value);
 nbkd_status nbkd_get_tuning(const char *name, double *value);
 /* 1 if a tree of `nodes` nodes takes the collect kernel's wide-address
  * instance under the current "collect_wide_addr" setting, else 0.  NEW. */
 int32_t nbkd_collect_wide_addr(uint64_t nodes);
+/* The kNN collect kernel's instance for a tree of `points` points and `nodes`
+ * nodes built with `leaf_size`, under the current knobs: bit 0 set = the
+ * one-chunk instance (leaf size <= 64: every leaf is staged whole, once);
+ * bit 1 set = 32-bit byte offsets (the walk's, and for the one-chunk
+ * instance also its staging loads': points * 16, points / 8 * 24 and
+ * nodes * 32 must all be below 2^32).  NEW. */
+int32_t nbkd_collect_instance(int32_t leaf_size, uint64_t points, uint64_t nodes);
+/* Those three staging bounds one by one: bit 0 set = the point offsets fit
+ * (points padded to a multiple of 8, times 16 B), bit 1 = the group-box
+ * offsets (24 B per 8 points), bit 2 = the leaf-box offsets (32 B per node).
+ * NEW. */
+int32_t nbkd_collect_stage_offsets(uint64_t points, uint64_t nodes);
 
 /* The calling thread's interrupt check: host-buffer query calls (kNN, k-th
  * distance, radius count) call fn(user) between batches and stop with

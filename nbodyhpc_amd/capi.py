@@ -97,6 +97,8 @@ _PROTOS = {
     "nbkd_set_interrupt": (_i32, [_c_p, _c_p]),
     "nbkd_get_tuning": (_i32, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double)]),
     "nbkd_collect_wide_addr": (_i32, [_u64]),
+    "nbkd_collect_instance": (_i32, [_i32, _u64, _u64]),
+    "nbkd_collect_stage_offsets": (_i32, [_u64, _u64]),
     "nbkd_comm_probe": (_i32, []),
     "nbkd_comm_unique_id": (_i32, [_c_p]),
     "nbkd_comm_init": (_i32, [_c_p, _i32, _i32, _i32, ctypes.POINTER(_c_p)]),
@@ -594,6 +596,22 @@ def collect_wide_addr(nodes):
     """nbkd_collect_wide_addr: whether a tree of `nodes` nodes takes the collect
     kernel's wide-address instance (the "collect_wide_addr" knob forces it)."""
     return bool(lib().nbkd_collect_wide_addr(int(nodes)))
+
+
+def collect_instance(leafsize, points, nodes):
+    """nbkd_collect_instance: (one_chunk, narrow) -- whether a tree of `points`
+    points and `nodes` nodes built with `leafsize` takes the collect kernel's
+    one-chunk instance (leaf size <= 64; the "collect_one_chunk" knob turns it
+    off), and whether its loads take 32-bit byte offsets."""
+    v = lib().nbkd_collect_instance(int(leafsize), int(points), int(nodes))
+    return bool(v & 1), bool(v & 2)
+
+
+def collect_stage_offsets(points, nodes):
+    """nbkd_collect_stage_offsets: which of the one-chunk instance's staging
+    offsets fit 32 bits, as (points, group boxes, leaf boxes)."""
+    v = lib().nbkd_collect_stage_offsets(int(points), int(nodes))
+    return bool(v & 1), bool(v & 2), bool(v & 4)
 
 
 def timing_enable(on=True):

@@ -269,10 +269,10 @@ void tree_free(void *p) {
 
 namespace {
 // nbkd_set_tuning knobs (process-wide); defaults are the measured optima
-std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0}, {0.0}, {0.0}};
+std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0}, {0.0}, {0.0}, {1.0}};
 const char *const g_tune_names[TUNE_N] = {"knn_seed_margin", "candidate_bytes", "host_batch",
                                           "host_threads", "self_order", "pinned_bytes",
-                                          "collect_wide_addr"};
+                                          "collect_wide_addr", "collect_one_chunk"};
 thread_local nbkd_interrupt_fn t_intr = nullptr;
 thread_local void *t_intr_user = nullptr;
 } // namespace
@@ -1037,6 +1037,16 @@ nbkd_status nbkd_set_tuning(const char *name, double value) {
 }
 
 int32_t nbkd_collect_wide_addr(uint64_t nodes) { return collect_wide_addr(nodes) ? 1 : 0; }
+
+int32_t nbkd_collect_instance(int32_t leaf_size, uint64_t points, uint64_t nodes) {
+    // as build_tree: the effective leaf size and the padded point count
+    const int leaf = std::max(leaf_size, 16);
+    return collect_instance(leaf, (points + 7) / 8 * 8, nodes);
+}
+
+int32_t nbkd_collect_stage_offsets(uint64_t points, uint64_t nodes) {
+    return collect_stage_narrow_bits(points > ~7ull ? points : (points + 7) / 8 * 8, nodes);
+}
 
 nbkd_status nbkd_get_tuning(const char *name, double *value) {
     if (!name || !value) {

@@ -236,6 +236,7 @@ enum TuneId {
     TUNE_SELF_ORDER,
     TUNE_PINNED_BYTES,
     TUNE_COLLECT_WIDE,
+    TUNE_COLLECT_ONE,
     TUNE_N
 };
 // host memcpy split over the library's copy threads (api.cpp): the host-buffer
@@ -367,6 +368,18 @@ uint32_t collect_capacity(int k);
 // with 32-bit offsets (every box offset, id * 32 B, then fits 32 bits).
 // nbkd_set_tuning("collect_wide_addr", 1) forces the wide one.
 bool collect_wide_addr(uint64_t nnodes);
+// The collect kernel's instance for a tree of effective leaf size `leaf`, n8
+// padded points and nnodes nodes: bit 0 = the one-chunk instance (every leaf
+// is one staged chunk: leaf <= 64, so the tree has no hinfo;
+// nbkd_set_tuning("collect_one_chunk", 0) turns it off), bit 1 = 32-bit
+// offsets (the walk's, as above, and for the one-chunk instance also its
+// staging loads', collect_stage_narrow_ok).
+int collect_instance(int leaf, uint64_t n8, uint64_t nnodes);
+// every byte offset of the one-chunk instance's staging loads fits 32 bits:
+// n8 * 16 (p4), n8 / 8 * 24 (ginfo), nnodes * 32 (leafinfo)
+bool collect_stage_narrow_ok(uint64_t n8, uint64_t nnodes);
+// the three bounds one by one: bit 0 p4, bit 1 ginfo, bit 2 leafinfo
+int collect_stage_narrow_bits(uint64_t n8, uint64_t nnodes);
 // seed-failure retry: adaptive per-query seeds written by the first select
 // pass (on by default) instead of a fixed 4x seed
 bool retry_adaptive();

@@ -116,6 +116,20 @@ constexpr int WPB = TB / 64;
 #define NBKD_PAIR_PREFETCH 0 // (with NBKD_PAIR_PAD) the next step's pair entry read one step early
 #endif
 
+//   NBKD_COLLECT_WPB   waves per block of the static first-pass collect (the
+//                      re-walk rounds and the selects keep TB = 256): a block's
+//                      wave slots and LDS return only when its slowest packet
+//                      ends, so smaller blocks fill slots sooner.  Step per
+//                      1e8 queries with the one-chunk instance, 4 / 2 / 1
+//                      waves: 46.01 / 45.84 / 45.56 ms, collect 32.42 / 32.13 /
+//                      31.88 (profiles/r10a_collect_ab.txt); every round of 1
+//                      below every round of 4 by more than the spread, 2 not
+#ifndef NBKD_COLLECT_WPB
+#define NBKD_COLLECT_WPB 1
+#endif
+constexpr int CWPB = NBKD_COLLECT_WPB; // 1, 2 or 4
+static_assert(CWPB == 1 || CWPB == 2 || CWPB == 4, "NBKD_COLLECT_WPB");
+
 constexpr int NB = 16; // distance buckets of the bound histogram
 
 // Bound tightening without a top-k: the seed ball [0, S) is cut into NB
@@ -185,6 +199,35 @@ struct CollectLdsG {
     uint8_t slot[64];            // lanes needing the leaf, compacted
 };
 
+// The staging of a whole leaf of cn <= GCHUNK points at position pa (the
+// one-chunk instance, grp_packet ONE) where every byte offset into p4, ginfo
+// and leafinfo fits 32 bits (collect_stage_narrow_ok): each source is its
+// table's uniform base plus a 32-bit per-lane byte offset, so the loads take
+// the SGPR-base form and no 64-bit address is formed per leaf.  The same
+// lanes load the same bytes as NBKD_COLLECT_STAGE_G; the group boxes' lanes
+// (6 per group, fewer than the points' 8) sit inside the points' region.
+__device__ __forceinline__ void stage_leaf_narrow(const float4 *__restrict__ p4,
+                                                  const float *__restrict__ ginfo,
+                                                  const uint32_t *__restrict__ linfo,
+                                                  CollectLdsG &W, const int lane, const uint32_t pa,
+                                                  const uint32_t cn, const uint32_t lnode) {
+    const uint32_t l4 = (uint32_t)lane * 4u;
+    if ((uint32_t)lane < cn) {
+        __builtin_amdgcn_global_load_lds(
+            (gas_ptr)(reinterpret_cast<const char *>(p4) + (size_t)((pa << 4) + 4u * l4)),
+            (las_ptr)W.p4, 16, 0, 0);
+        if ((uint32_t)lane < 6u * (cn / NBKD_GROUP))
+            __builtin_amdgcn_global_load_lds(
+                (gas_ptr)(reinterpret_cast<const char *>(ginfo) +
+                          (size_t)((pa / NBKD_GROUP) * 24u + l4)),
+                (las_ptr)W.gb, 4, 0, 0);
+    }
+    if (lane < 6)
+        __builtin_amdgcn_global_load_lds(
+            (gas_ptr)(reinterpret_cast<const char *>(linfo) + (size_t)((lnode << 5) + l4)),
+            (las_ptr)W.tb, 4, 0, 0);
+}
+
 // a chunk of CN points at LPOS, its group boxes and its tight box TBOX (6
 // words: lo.xyz, hi.xyz)
 #define NBKD_COLLECT_STAGE_G(LPOS, CN, TBOX)                                                       \
@@ -197,7 +240,7 @@ struct CollectLdsG {
 // st: node visits, leaves scanned, points staged, leaves reached, sparse
 // iterations, pair evaluations, then 6 phase clocks, then lanes needing a
 // staged chunk summed over chunks (STATS only)
-template <bool PER, bool M, bool STATS, bool AHEAD, bool NARROW>
+template <bool PER, bool M, bool STATS, bool AHEAD, bool NARROW, bool ONE>
 __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__restrict__ ginfo,
                                            const uint32_t *__restrict__ linfo,
                                            const float *__restrict__ hinfo,
@@ -257,15 +300,19 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
             // under the leaf's tight box (leafinfo)
             const uint32_t lend = ea;
             const uint32_t lc = lend - pa;
-            const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
+            const bool halves = !ONE && hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
             const uint32_t hm = (lc / 2) / 8 * 8;
             const float *const lbox = halves ? hinfo + 12 * (size_t)lnode
                                              : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode;
             uint32_t c0 = pa;
-            uint32_t cn = halves ? hm : min((uint32_t)GCHUNK, lc);
+            // ONE: the leaf is its own single chunk
+            uint32_t cn = ONE ? lc : (halves ? hm : min((uint32_t)GCHUNK, lc));
             if constexpr (!AHEAD) {
                 if constexpr (STATS) ++st[3]; // leaves reached (staged), needed by some lane or not
-                NBKD_COLLECT_STAGE_G(pa, cn, lbox);
+                if constexpr (ONE && NARROW)
+                    stage_leaf_narrow(t.p4, ginfo, linfo, W, lane, pa, cn, lnode);
+                else
+                    NBKD_COLLECT_STAGE_G(pa, cn, lbox);
             }
             NBKD_PH(0);
             // Tried and dropped (r04aa): pulling the next leaf's lines (points,
@@ -420,7 +467,7 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                     NBKD_PH(4);
                 }
                 c0 += cn;
-                if (c0 >= lend) {
+                if (ONE || c0 >= lend) {
                     if constexpr (STATS) st[1] += any_leaf ? 1 : 0;
                     // tighten: smallest bucket edge with >= k candidates below it
                     // (after every leaf that added candidates; re-tightening only
@@ -471,10 +518,16 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
             lnode = wk.node;
             if constexpr (STATS) ++st[3];
             const uint32_t lc = ea - pa;
-            const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
-            NBKD_COLLECT_STAGE_G(pa, halves ? (lc / 2) / 8 * 8 : min((uint32_t)GCHUNK, lc),
-                                 halves ? hinfo + 12 * (size_t)lnode
-                                        : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode);
+            if constexpr (ONE && NARROW) {
+                stage_leaf_narrow(t.p4, ginfo, linfo, W, lane, pa, lc, lnode);
+            } else if constexpr (ONE) {
+                NBKD_COLLECT_STAGE_G(pa, lc, reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode);
+            } else {
+                const bool halves = hinfo != nullptr && lc > (uint32_t)GCHUNK && lc <= 2u * GCHUNK;
+                NBKD_COLLECT_STAGE_G(pa, halves ? (lc / 2) / 8 * 8 : min((uint32_t)GCHUNK, lc),
+                                     halves ? hinfo + 12 * (size_t)lnode
+                                            : reinterpret_cast<const float *>(linfo) + 8 * (size_t)lnode);
+            }
         }
     }
     NBKD_PH(0);
@@ -482,7 +535,7 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
 }
 
 // one packet of the collect pass
-template <bool PER, bool STATS, bool AHEAD, bool NARROW>
+template <bool PER, bool STATS, bool AHEAD, bool NARROW, bool ONE>
 __device__ __forceinline__ void collect_packet(
     const DevTree &t, const float *__restrict__ ginfo, const uint32_t *__restrict__ linfo,
     const float *__restrict__ hinfo, const float *__restrict__ q, const uint32_t *__restrict__ order,
@@ -536,10 +589,10 @@ __device__ __forceinline__ void collect_packet(
         plain = __all(wf);
     }
     if (plain)
-        grp_packet<PER, false, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, false, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                              s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     else
-        grp_packet<PER, PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                            s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     if (valid) ccount[gq] = cnt;
     // the final bound: at least k candidates lie strictly below it (bound
@@ -568,8 +621,8 @@ __device__ __forceinline__ void collect_packet(
 // A static pass launches one wave per packet; a device-counted pass (the
 // retry rounds: LOOP) a fixed grid that strides over its packets.  Only the
 // LOOP instance carries the loop (in the first pass it cost a 12-28 B spill).
-template <bool PER, int OCC, bool STATS, bool LOOP, bool AHEAD, bool NARROW>
-__global__ void __launch_bounds__(TB, OCC)
+template <bool PER, int OCC, bool STATS, bool LOOP, bool AHEAD, bool NARROW, bool ONE>
+__global__ void __launch_bounds__(64 * (LOOP ? WPB : CWPB), OCC)
 knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
                        const uint32_t *__restrict__ linfo, const float *__restrict__ hinfo,
                        const float *__restrict__ q,
@@ -578,7 +631,10 @@ knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
                        uint2 *__restrict__ cand, uint32_t capg,
                        uint32_t *__restrict__ ccount, unsigned long long *__restrict__ stats,
                        bool xcd, float *__restrict__ kbound) {
-    __shared__ CollectLdsG Wl[WPB];
+    // waves per block: the static first pass has its own (CWPB), the re-walk
+    // rounds' fixed grid keeps the selects' block
+    constexpr int BW = LOOP ? WPB : CWPB;
+    __shared__ CollectLdsG Wl[BW];
     const int lane = threadIdx.x & 63, wave = wave_id();
     CollectLdsG &W = Wl[wave];
     const uint32_t m = span_m(span);
@@ -587,14 +643,14 @@ knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
     if constexpr (LOOP) {
         for (uint32_t pk = bid * WPB + wave; pk < npk; pk += gridDim.x * WPB) {
             wave_sync(); // the previous packet's LDS reads are done
-            collect_packet<PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
         }
     } else {
-        const uint32_t pk = bid * WPB + wave;
+        const uint32_t pk = bid * BW + wave;
         if (pk < npk)
-            collect_packet<PER, STATS, AHEAD, NARROW>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
     }
@@ -1315,7 +1371,7 @@ void launch_collect(const Tree &t, const float *q, const uint32_t *order, QSpan 
     const unsigned blocks =
         span.count ? std::min<unsigned>(resident_blocks(),
                                         (unsigned)((((uint64_t)m + qpp - 1) / qpp + WPB - 1) / WPB))
-                   : (unsigned)((((uint64_t)m + qpp - 1) / qpp + WPB - 1) / WPB);
+                   : (unsigned)((((uint64_t)m + qpp - 1) / qpp + CWPB - 1) / CWPB);
     // the bound histogram's 8-bit bucket counts are exact while the cumulative
     // count below the k-th's bucket is < 256, i.e. for k <= 255 (a wrapped or
     // carried byte can only make a larger cumulative count); above, no tightening
@@ -1329,17 +1385,26 @@ void launch_collect(const Tree &t, const float *q, const uint32_t *order, QSpan 
         // the re-walk rounds are timed as one phase by the caller (query.hip)
         TimedScope ts(name, s, !retry);
         // the walk's node and box loads take 32-bit offsets wherever the tree allows
-        const bool narrow = !collect_wide_addr((uint64_t)t.nnodes);
-#define NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, NARROW)                                            \
-    knn_collect_grp_kernel<PER, 8, STATS, LOOP, AHEAD, NARROW><<<blocks, TB, 0, s>>>(              \
-        view(t), t.ginfo, t.leafinfo, t.hinfo, q, order, span, k, tg, seed_mul, qpp, cand, capg,   \
-        ccount, STP, XCD, kbound)
+        // and a tree whose leaves are one staged chunk each takes the one-chunk
+        // instance, whose staging needs its own offsets to fit for the narrow form
+        const int inst = collect_instance(t.leaf, t.n8, t.nnodes);
+        const bool one = (inst & 1) != 0, narrow = (inst & 2) != 0;
+#define NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, NARROW, ONE)                                       \
+    knn_collect_grp_kernel<PER, 8, STATS, LOOP, AHEAD, NARROW, ONE>                                \
+        <<<blocks, 64 * ((LOOP) ? WPB : CWPB), 0, s>>>(                                            \
+            view(t), t.ginfo, t.leafinfo, t.hinfo, q, order, span, k, tg, seed_mul, qpp, cand,     \
+            capg, ccount, STP, XCD, kbound)
 #define NBKD_GRP(STATS, LOOP, AHEAD, STP, XCD)                                                     \
     do {                                                                                           \
-        if (narrow)                                                                                \
-            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, true);                                         \
+        if (one) {                                                                                 \
+            if (narrow)                                                                            \
+                NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, true, true);                               \
+            else                                                                                   \
+                NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, false, true);                              \
+        } else if (narrow)                                                                         \
+            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, true, false);                                  \
         else                                                                                       \
-            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, false);                                        \
+            NBKD_GRP_(STATS, LOOP, AHEAD, STP, XCD, false, false);                                 \
     } while (0)
         if (span.count)
             NBKD_GRP(false, true, NBKD_LOOP_AHEAD != 0, nullptr, false);
@@ -1459,6 +1524,25 @@ bool retry_adaptive() {
 
 bool collect_wide_addr(uint64_t nnodes) {
     return !dev::walk_narrow_ok(nnodes) || tuning(TUNE_COLLECT_WIDE) != 0.0;
+}
+
+int collect_stage_narrow_bits(uint64_t n8, uint64_t nnodes) {
+    // past the largest byte offsets of the one-chunk instance's staging loads:
+    // p4 (16 B per point), ginfo (24 B per group of 8), leafinfo (32 B per node)
+    constexpr uint64_t LIM = 1ull << 32;
+    const bool big = n8 >= LIM || nnodes >= LIM; // (the products below cannot wrap)
+    return (!big && n8 * 16u < LIM ? 1 : 0) | (!big && (n8 / NBKD_GROUP) * 24u < LIM ? 2 : 0) |
+           (!big && nnodes * 32u < LIM ? 4 : 0);
+}
+
+bool collect_stage_narrow_ok(uint64_t n8, uint64_t nnodes) {
+    return collect_stage_narrow_bits(n8, nnodes) == 7;
+}
+
+int collect_instance(int leaf, uint64_t n8, uint64_t nnodes) {
+    const bool one = leaf <= GCHUNK && tuning(TUNE_COLLECT_ONE) != 0.0;
+    const bool narrow = !collect_wide_addr(nnodes) && (!one || collect_stage_narrow_ok(n8, nnodes));
+    return (one ? 1 : 0) | (narrow ? 2 : 0);
 }
 
 uint32_t collect_capacity(int k) {
