@@ -130,6 +130,41 @@ constexpr int WPB = TB / 64;
 constexpr int CWPB = NBKD_COLLECT_WPB; // 1, 2 or 4
 static_assert(CWPB == 1 || CWPB == 2 || CWPB == 4, "NBKD_COLLECT_WPB");
 
+// Round-11 scan loop (same traversal, same bound arithmetic, same column
+// order, same rows; profiles/r11a_collect_ab.txt):
+//   NBKD_SCAN_LEAN     fewer vector instructions per scan step and per leaf:
+//                      pair entries slot << 4 | group (the query's LDS offset
+//                      is one AND of the entry), the owner lane no longer in
+//                      the entry but in an 8-byte per-slot record beside the
+//                      bucket factor, read with the query and the point (no
+//                      fourth dependent LDS round trip in the hit region, no
+//                      owner read in the group-test loop); histogram rows
+//                      [lane][4 words] (the hit's word address is one AND-OR,
+//                      the tighten reads one b128); the tighten's byte prefix
+//                      sums by two shift-adds per word instead of a quarter-
+//                      rate multiply; the returning atomic's operand doubles
+//                      as the DPP moves' old value (no zero moves)
+//   NBKD_SCAN_TWO      (with NBKD_SCAN_LEAN) one loop iteration handles scan
+//                      steps t and t + 1: both pair entries, then all six
+//                      reads, both distances and ballots, the two returning
+//                      atomics back to back in step order (a wave's LDS
+//                      operations execute in issue order, so every column
+//                      takes the same slots), then the two hit regions in
+//                      step order; an odd step count ends in a single step.
+//                      In the static first pass's kernels only (56 VGPRs):
+//                      the re-walk rounds' and the instrumented instances
+//                      sit at the 64-VGPR cap of 8 waves per SIMD and would
+//                      spill 12-36 B, so they keep the single step
+#ifndef NBKD_SCAN_LEAN
+#define NBKD_SCAN_LEAN 1
+#endif
+#ifndef NBKD_SCAN_TWO
+#define NBKD_SCAN_TWO 1
+#endif
+#if NBKD_SCAN_LEAN && !(NBKD_PAIR_PAD && NBKD_PAIR_ATOMIC && NBKD_COL_ROWMAJOR)
+#error "NBKD_SCAN_LEAN needs NBKD_PAIR_PAD, NBKD_PAIR_ATOMIC and NBKD_COL_ROWMAJOR"
+#endif
+
 constexpr int NB = 16; // distance buckets of the bound histogram
 
 // Bound tightening without a top-k: the seed ball [0, S) is cut into NB
@@ -187,6 +222,29 @@ constexpr uint32_t PR_OWNER = NBKD_PAIR_PAD ? 7 : 6, PR_G = NBKD_PAIR_PAD ? 13 :
 constexpr uint32_t PR_SLOT = (1u << PR_OWNER) - 1u;
 constexpr uint32_t PAIR_DUMMY = 64u;
 
+#if NBKD_SCAN_LEAN
+// pair entries (16 bits): compacted slot << 4 | group; slot 64 is the padding
+// pairs' query.  entry & PR_QOFF is the byte offset of sq[slot], half of it
+// that of rec[slot].
+constexpr uint32_t PR_QOFF = 0x7F0u, PR_GRP = 7u;
+struct SlotRec {
+    float scl;      // the owner's bucket factor (d2_bucket)
+    uint32_t own16; // owner lane * 16: the byte offset of its histogram row, 4 x that of its count
+};
+// 5120 B: 32 waves per CU fit the CU's 160 KiB
+struct CollectLdsG {
+    float4 sq[64 + 1];         // per slot: query xyz + bound (+ the padding pairs' query)
+    uint32_t cnt[64];          // per lane: candidates in its column
+    uint32_t hist[64][NB / 4]; // per lane: the bound histogram's 16 byte counters
+    float4 p4[GCHUNK];         // the staged points: x, y, z, original id bits
+    float gb[6 * GMAX];        // the chunk's group boxes (lo.x, hi.x, lo.y, hi.y, lo.z, hi.z)
+    float tb[8];               // the leaf's tight box (leafinfo words 0..5)
+    SlotRec rec[64 + 1];       // per slot (the padding slot's is read, never used)
+    uint16_t pairs[64 * GMAX]; // the pair list
+};
+static_assert(sizeof(CollectLdsG) <= 5120, "CollectLdsG: 32 waves per CU");
+static_assert(offsetof(CollectLdsG, hist) % 16 == 0 && offsetof(CollectLdsG, p4) % 16 == 0, "b128");
+#else
 struct CollectLdsG {
     float4 sq[64 + NBKD_PAIR_PAD]; // per lane: query xyz + bound (+ the padding pairs' query)
     float scl[64]; // per lane: bucket factor (d2_bucket)
@@ -198,6 +256,7 @@ struct CollectLdsG {
     uint16_t pairs[64 * GMAX];   // (slot, lane, group) pairs: slot | lane << PR_OWNER | group << PR_G
     uint8_t slot[64];            // lanes needing the leaf, compacted
 };
+#endif
 
 // The staging of a whole leaf of cn <= GCHUNK points at position pa (the
 // one-chunk instance, grp_packet ONE) where every byte offset into p4, ginfo
@@ -237,10 +296,109 @@ __device__ __forceinline__ void stage_leaf_narrow(const float4 *__restrict__ p4,
         glds_f32((TBOX), W.tb, lane, 6);                                                           \
     } while (0)
 
+#if NBKD_SCAN_LEAN
+// One scan step: every lane holds one (pair, point) evaluation, a pair's 8
+// points on 8 consecutive lanes (padding pairs never hit).
+struct ScanLane {      // what a lane keeps for all its steps
+    uint32_t p_off;    // (lane & 7) * 16: its point inside its pair's group
+    uint32_t first;    // lane & ~7: its pair's first lane
+    uint32_t below;    // mask of its pair's lanes below it
+    bool last;         // its pair's last lane issues the pair's returning atomic
+};
+struct ScanStep {
+    float4 qq, pp; // the pair's query (w: its bound) and the lane's point (w: original id bits)
+    SlotRec rc;
+};
+
+// the three LDS reads of a step, in flight together
+__device__ __forceinline__ ScanStep scan_read(const CollectLdsG &W, const ScanLane &sl,
+                                              const uint32_t pr) {
+    const uint32_t qo = pr & PR_QOFF;
+    ScanStep s;
+    s.qq = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(W.sq) + qo);
+    s.pp = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(W.p4) +
+                                             (((pr & PR_GRP) << 7) | sl.p_off));
+    s.rc = *reinterpret_cast<const SlotRec *>(reinterpret_cast<const char *>(W.rec) + (qo >> 1));
+    return s;
+}
+
+// point_d2_fast's operations in its order, one plain instruction each (three
+// differences, three products, two sums).  Left to the compiler, the plain
+// metric's x and z go through packed forms that need operand moves (two per
+// step; thirteen when two steps are in flight).  The periodic metric keeps
+// the compiled form.
+__device__ __forceinline__ float scan_sub(float a, float b) {
+    float r;
+    asm("v_sub_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float scan_mul(float a, float b) {
+    float r;
+    asm("v_mul_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float scan_add(float a, float b) {
+    float r;
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <bool M>
+__device__ __forceinline__ float scan_d2(const ScanStep &s, const float L) {
+    if constexpr (M) {
+        return point_d2_fast<true>(s.qq.x, s.qq.y, s.qq.z, s.pp.x, s.pp.y, s.pp.z, L);
+    } else {
+        const float dx = scan_sub(s.pp.x, s.qq.x), dy = scan_sub(s.pp.y, s.qq.y);
+        const float dz = scan_sub(s.pp.z, s.qq.z);
+        const float a = scan_mul(dx, dx), b = scan_mul(dy, dy), c = scan_mul(dz, dz);
+        return scan_add(scan_add(a, b), c);
+    }
+}
+
+// The hits of a pair (8 consecutive lanes, one owner) take consecutive column
+// slots: one returning atomic by the pair's last lane (its operand, the pair's
+// hit count, stands in the other lanes, which the broadcast overwrites).
+// cnt_off: the byte offset of the owner's count, own16 / 4.
+__device__ __forceinline__ uint32_t scan_claim(CollectLdsG &W, const ScanLane &sl,
+                                               const uint32_t cnt_off, const uint32_t gbits) {
+    uint32_t base = (uint32_t)__popc(gbits);
+    if (sl.last && gbits != 0u)
+        base = atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(W.cnt) + cnt_off),
+                         base);
+    return base;
+}
+
+// the last lane's value to its pair's 8 lanes by two DPP moves: quad_perm
+// [3,3,3,3] (lanes 0-3 of the pair read lane 3, 4-7 lane 7), then
+// row_half_mirror into banks 0 and 2 only (lanes 0-3 read 7-4)
+__device__ __forceinline__ uint32_t scan_bcast(uint32_t base) {
+    base = (uint32_t)__builtin_amdgcn_update_dpp((int)base, (int)base, 0xFF, 0xF, 0xF, false);
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)base, (int)base, 0x141, 0xF, 0x5, false);
+}
+
+// a hit: its bucket counted in the owner's histogram row, the candidate (d2,
+// the point's original id: the selects write it without a gather) stored at a
+// 32-bit byte offset from the packet's (SGPR) column base.  A row past capg
+// is a failure whose column is never read (both selects): its extra hits
+// overwrite its last slot (no branch).  capg_half = capg / 2 (capg is even):
+// own16 * capg_half = owner * capg * 8.
+__device__ __forceinline__ void scan_hit(CollectLdsG &W, const ScanLane &sl, const ScanStep &s,
+                                         const float d, const uint32_t gbits, const uint32_t base,
+                                         const uint32_t capg, const uint32_t capg_half,
+                                         uint2 *__restrict__ col) {
+    const uint32_t j = d2_bucket(d, s.rc.scl);
+    atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(W.hist) +
+                                           ((j & 12u) | s.rc.own16)), 1u << ((j << 3) & 31u));
+    const uint32_t sw = min(base + (uint32_t)__popc(gbits & sl.below), capg - 1u);
+    const uint32_t off = __umul24(s.rc.own16, capg_half) + (sw << 3);
+    *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(col) + off) =
+        make_uint2(__float_as_uint(d), __float_as_uint(s.pp.w));
+}
+#endif
+
 // st: node visits, leaves scanned, points staged, leaves reached, sparse
 // iterations, pair evaluations, then 6 phase clocks, then lanes needing a
 // staged chunk summed over chunks (STATS only)
-template <bool PER, bool M, bool STATS, bool AHEAD, bool NARROW, bool ONE>
+template <bool PER, bool M, bool STATS, bool AHEAD, bool NARROW, bool ONE, bool TWO>
 __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__restrict__ ginfo,
                                            const uint32_t *__restrict__ linfo,
                                            const float *__restrict__ hinfo,
@@ -252,6 +410,11 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                                            uint32_t (&st)[13]) {
     const float L = t.box;
     uint32_t last_cnt = 0;
+#if NBKD_SCAN_LEAN
+    const uint32_t l7 = (uint32_t)lane & 7u;
+    const ScanLane sln = {l7 << 4, (uint32_t)lane & ~7u, (1u << l7) - 1u, l7 == 7u};
+    const uint32_t capg_half = capg >> 1;
+#endif
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
     PacketWalk wk;
@@ -343,14 +506,19 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                     // (indexed by lane, owners 16 apart hit the same banks)
                     if (need) {
                         const uint32_t r = mbcnt64(nm);
-                        W.slot[r] = (uint8_t)lane;
                         W.sq[r] = make_float4(qx, qy, qz, kth);
+#if NBKD_SCAN_LEAN
+                        W.rec[r] = SlotRec{nb_over_s, (uint32_t)lane << 4};
+#else
+                        W.slot[r] = (uint8_t)lane;
                         W.scl[r] = nb_over_s;
+#endif
                     }
                     wave_sync();
                     // (needing lane, group) box tests, 8 lanes per needing lane (one
                     // per group); the groups reached become the pair list, entries
-                    // slot | owner lane << 6 | group << 12
+                    // slot << 4 | group (NBKD_SCAN_LEAN; else slot | owner lane <<
+                    // PR_OWNER | group << PR_G)
                     uint32_t np = 0;
                     const uint32_t ntest = nneed * GMAX;
 #pragma unroll 1
@@ -358,10 +526,14 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                         const uint32_t ti = t0 + lane;
                         const uint32_t g = ti % GMAX;
                         const uint32_t sl = ti / GMAX;
+#if !NBKD_SCAN_LEAN
                         uint32_t owner = 0;
+#endif
                         bool hit = false;
                         if (ti < ntest && g < ng) {
+#if !NBKD_SCAN_LEAN
                             owner = W.slot[sl];
+#endif
                             const float4 qq = W.sq[sl];
                             const float gbx[6] = {W.gb[6 * g], W.gb[6 * g + 1], W.gb[6 * g + 2],
                                                   W.gb[6 * g + 3], W.gb[6 * g + 4], W.gb[6 * g + 5]};
@@ -369,14 +541,19 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                         }
                         const uint64_t hm = __ballot(hit);
                         if (hit)
+#if NBKD_SCAN_LEAN
+                            W.pairs[np + mbcnt64(hm)] = (uint16_t)((sl << 4) | g);
+#else
                             W.pairs[np + mbcnt64(hm)] = (uint16_t)(sl | (owner << PR_OWNER) | (g << PR_G));
+#endif
                         np += (uint32_t)__popcll(hm);
                     }
                     if constexpr (STATS) st[5] += np * NBKD_GROUP; // (pair, point) evaluations
 #if NBKD_PAIR_PAD
                     // whole scan steps: the last one's missing pairs never hit
                     const uint32_t npp = (np + 7u) & ~7u;
-                    if ((uint32_t)lane < npp - np) W.pairs[np + lane] = (uint16_t)PAIR_DUMMY;
+                    if ((uint32_t)lane < npp - np)
+                        W.pairs[np + lane] = (uint16_t)(NBKD_SCAN_LEAN ? PAIR_DUMMY << 4 : PAIR_DUMMY);
                     np = npp;
 #endif
                     NBKD_PH(2);
@@ -389,6 +566,43 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                     // arithmetic costs more issue than the atomics' waits.
                     // each pair's 8 points spread over 8 consecutive lanes
                     const uint32_t ntrip = np * NBKD_GROUP;
+#if NBKD_SCAN_LEAN
+                    // every lane of every step holds a pair: entry (t0 + lane) / 8
+                    const uint16_t *const pl = W.pairs + ((uint32_t)lane >> 3);
+                    uint32_t t0 = 0;
+                    // steps t0 and t0 + 64 together; everything that touches a
+                    // column (the returning atomics, the stores) in step order
+#pragma unroll 1
+                    for (; TWO && t0 + 128 <= ntrip; t0 += 128) {
+                        if constexpr (STATS) st[4] += 2;
+                        const uint32_t pra = pl[t0 >> 3], prb = pl[(t0 >> 3) + 8];
+                        const ScanStep a = scan_read(W, sln, pra), b = scan_read(W, sln, prb);
+                        const float da = scan_d2<M>(a, L), db = scan_d2<M>(b, L);
+                        const bool hita = da < a.qq.w, hitb = db < b.qq.w;
+                        const uint32_t ga = (uint32_t)(__ballot(hita) >> sln.first) & 0xFFu;
+                        const uint32_t gb = (uint32_t)(__ballot(hitb) >> sln.first) & 0xFFu;
+                        // both count offsets before the first atomic, so that the
+                        // second atomic waits for no read behind the first
+                        const uint32_t ca = a.rc.own16 >> 2, cb = b.rc.own16 >> 2;
+                        asm volatile("" : : "v"(ca), "v"(cb));
+                        uint32_t ba = scan_claim(W, sln, ca, ga);
+                        uint32_t bb = scan_claim(W, sln, cb, gb);
+                        ba = scan_bcast(ba);
+                        bb = scan_bcast(bb);
+                        if (hita) scan_hit(W, sln, a, da, ga, ba, capg, capg_half, col);
+                        if (hitb) scan_hit(W, sln, b, db, gb, bb, capg, capg_half, col);
+                    }
+#pragma unroll 1
+                    for (; t0 < ntrip; t0 += 64) {
+                        if constexpr (STATS) ++st[4];
+                        const ScanStep a = scan_read(W, sln, pl[t0 >> 3]);
+                        const float da = scan_d2<M>(a, L);
+                        const bool hita = da < a.qq.w;
+                        const uint32_t ga = (uint32_t)(__ballot(hita) >> sln.first) & 0xFFu;
+                        const uint32_t ba = scan_bcast(scan_claim(W, sln, a.rc.own16 >> 2, ga));
+                        if (hita) scan_hit(W, sln, a, da, ga, ba, capg, capg_half, col);
+                    }
+#else
 #if NBKD_PAIR_PAD && NBKD_PAIR_PREFETCH
                     // the next step's pair entry is read while this step computes
                     uint32_t pr_next = ntrip ? W.pairs[(uint32_t)lane >> 3] : 0u;
@@ -462,6 +676,7 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                             }
                         }
                     }
+#endif
                     wave_sync();
                     cnt = W.cnt[lane];
                     NBKD_PH(4);
@@ -479,10 +694,22 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
                         wave_sync();
                         if (upd) {
                             last_cnt = cnt;
+#if NBKD_SCAN_LEAN
+                            // byte prefix sums of the lane's four histogram words: h *
+                            // 0x01010101 (mod 2^32) as two shift-adds
+                            const uint4 hw = *reinterpret_cast<const uint4 *>(W.hist[lane]);
+                            uint32_t q0 = hw.x + (hw.x << 8), q1 = hw.y + (hw.y << 8);
+                            uint32_t q2 = hw.z + (hw.z << 8), q3 = hw.w + (hw.w << 8);
+                            // (opaque here, or the two steps are folded back into the multiply)
+                            asm("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3));
+                            const uint32_t p0 = q0 + (q0 << 16), p1 = q1 + (q1 << 16);
+                            const uint32_t p2 = q2 + (q2 << 16), p3 = q3 + (q3 << 16);
+#else
                             const uint32_t p0 = W.hist[0][lane] * 0x01010101u;
                             const uint32_t p1 = W.hist[1][lane] * 0x01010101u;
                             const uint32_t p2 = W.hist[2][lane] * 0x01010101u;
                             const uint32_t p3 = W.hist[3][lane] * 0x01010101u;
+#endif
                             const uint32_t c0w = p0 >> 24, c1w = c0w + (p1 >> 24), c2w = c1w + (p2 >> 24);
                             const uint32_t kk = (uint32_t)kq;
                             const uint32_t w = c0w >= kk ? 0u : c1w >= kk ? 1u : c2w >= kk ? 2u : 3u;
@@ -535,7 +762,7 @@ __device__ __forceinline__ void grp_packet(const DevTree &t, const float *__rest
 }
 
 // one packet of the collect pass
-template <bool PER, bool STATS, bool AHEAD, bool NARROW, bool ONE>
+template <bool PER, bool STATS, bool AHEAD, bool NARROW, bool ONE, bool TWO>
 __device__ __forceinline__ void collect_packet(
     const DevTree &t, const float *__restrict__ ginfo, const uint32_t *__restrict__ linfo,
     const float *__restrict__ hinfo, const float *__restrict__ q, const uint32_t *__restrict__ order,
@@ -562,8 +789,12 @@ __device__ __forceinline__ void collect_packet(
     const bool fin = seed < FLT_MAX && seed >= 1e-30f;
     const float s_over_nb = fin ? seed * (1.0f / NB) : (seed > 0.0f ? INFINITY : 0.0f);
     const float nb_over_s = fin ? (float)NB / seed * 1.00000095367431640625f : 0.0f;
+#if NBKD_SCAN_LEAN
+    *reinterpret_cast<uint4 *>(W.hist[lane]) = make_uint4(0u, 0u, 0u, 0u);
+#else
 #pragma unroll
     for (int w = 0; w < NB / 4; ++w) W.hist[w][lane] = 0u;
+#endif
 #if NBKD_PAIR_PAD
     if (lane == 0) W.sq[PAIR_DUMMY] = make_float4(0.0f, 0.0f, 0.0f, -INFINITY);
 #endif
@@ -589,10 +820,10 @@ __device__ __forceinline__ void collect_packet(
         plain = __all(wf);
     }
     if (plain)
-        grp_packet<PER, false, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, false, STATS, AHEAD, NARROW, ONE, TWO>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                              s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     else
-        grp_packet<PER, PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
+        grp_packet<PER, PER, STATS, AHEAD, NARROW, ONE, TWO>(t, ginfo, linfo, hinfo, W, lane, qx, qy, qz, kth,
                                            s_over_nb, nb_over_s, col, qpp, capg, kq, cnt, st);
     if (valid) ccount[gq] = cnt;
     // the final bound: at least k candidates lie strictly below it (bound
@@ -636,21 +867,22 @@ knn_collect_grp_kernel(DevTree t, const float *__restrict__ ginfo,
     constexpr int BW = LOOP ? WPB : CWPB;
     __shared__ CollectLdsG Wl[BW];
     const int lane = threadIdx.x & 63, wave = wave_id();
-    CollectLdsG &W = Wl[wave];
+    // NBKD_SCAN_LEAN, one wave per block: the LDS offsets are compile-time constants
+    CollectLdsG &W = Wl[NBKD_SCAN_LEAN != 0 && BW == 1 ? 0 : wave];
     const uint32_t m = span_m(span);
     const uint32_t npk = (m + qpp - 1) / qpp;
     const uint32_t bid = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
     if constexpr (LOOP) {
         for (uint32_t pk = bid * WPB + wave; pk < npk; pk += gridDim.x * WPB) {
             wave_sync(); // the previous packet's LDS reads are done
-            collect_packet<PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW, ONE, false>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
         }
     } else {
         const uint32_t pk = bid * BW + wave;
         if (pk < npk)
-            collect_packet<PER, STATS, AHEAD, NARROW, ONE>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
+            collect_packet<PER, STATS, AHEAD, NARROW, ONE, NBKD_SCAN_TWO != 0 && !STATS>(t, ginfo, linfo, hinfo, q, order, m, kq, tg, span.tg_pos,
                                               seed_mul, qpp, cand, capg, ccount, stats, kbound,
                                               W, lane, pk, span.out_list, span.out_count);
     }
@@ -1574,6 +1806,11 @@ nbkd_status launch_collect_pass(const Tree &t, const float *q, const uint32_t *o
                                 uint32_t capg, uint32_t *ccount, bool retry, float *kb,
                                 unsigned long long *stats, hipStream_t s) {
     if (span.m == 0) return NBKD_OK;
+    // the scan's column offset is (owner * 16) * (capg / 2), the selects' row stride capg / 2
+    if (capg & 1u) {
+        set_error("internal: odd candidate column capacity");
+        return NBKD_EINVAL;
+    }
     // k > 64: the collect kernel hands each query's final bound to the wave select
     float *kbound = k > 64 ? kb : nullptr;
     if (t.periodic)
