@@ -166,6 +166,69 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
                                  uint64_t *out_total, uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): anisotropic pair counts in one tree walk:
+ * every (query, point) pair classified on two coordinates about a line of
+ * sight along one coordinate axis.  DD(rp, pi), from which the projected
+ * correlation function wp(rp) is summed, and DD(s, mu), from which the
+ * multipoles xi_0, xi_2, xi_4 are.  Cross counts and DR / RR come from passing
+ * the other catalogue as the queries.
+ *   q          (m, 3) float32, host or device (NBKD_INPUT_DEVICE)
+ *   mode       NBKD_HIST2_RPPI or NBKD_HIST2_SMU
+ *   los        0, 1 or 2: the axis of the line of sight
+ *   edges1     (n1,) float32, host memory, ascending (equal neighbours allowed),
+ *              each finite and >= 0, 1 <= n1 <= NBKD_MAX_RADII: rp or s edges
+ *   edges2     (n2,) float32, host memory, under the same rules, 1 <= n2 <=
+ *              NBKD_MAX_LOS_BINS: pi edges, or mu edges, each then also <= 1
+ *   out_total  (n1, n2) row-major uint64, always host memory, required
+ * Per-axis quantities, for query i and tree point j, per axis a, in float32
+ * without fused multiply-adds: a_a = fl(d*d) with d = fl(p_a - q_a); on a
+ * periodic tree the smallest of the three squares of d, fl(d - L), fl(d + L).
+ * These are the terms the tree's d2 adds up; nothing here is a new metric.
+ *   pi2 = a_los
+ *   rp2 = fl(a_u + a_v), u < v the other two axes
+ *   s2  = fl(fl(a_x + a_y) + a_z) whatever los is: the d2 of
+ *         nbkd_query_ball_count, bit for bit
+ * Thresholds, formed on the host in float32: T1[k] = fl(edges1[k] * edges1[k]);
+ * RPPI: T2[l] = fl(edges2[l] * edges2[l]); SMU: M[l] = fl(edges2[l] * edges2[l]).
+ * A product that overflows counts as FLT_MAX (nbkd_query_ball_sum's rule).
+ * Bins, with the test written !(x <= t) as in nbkd_query_ball_hist:
+ *   RPPI  b1 = #{k : !(rp2 <= T1[k])},  b2 = #{l : !(pi2 <= T2[l])}
+ *   SMU   b1 = #{k : !(s2 <= T1[k])};  if b1 < n1,
+ *         b2 = #{l : !(pi2 <= fl(M[l] * s2))}
+ * The pair adds 1 to out_total[b1, b2] iff b1 < n1 and b2 < n2, otherwise
+ * nowhere.  Bins are differential in both directions: a cumulative table
+ * belongs to the caller.  Padding points are in no bin.
+ * By monotone rounding pi2 <= s2 always, so with a last mu edge of exactly 1
+ * every pair with b1 < n1 is counted, and the sum over b2 of row b1 equals the
+ * first difference of nbkd_query_ball_hist's totals at edges1.  A pair with
+ * s2 == 0 (the query itself, any coincident point) falls into bin (0, 0) in
+ * both modes.  Untested: coordinates so small that M[l] * s2 is subnormal.
+ * Counts are exact integers (integer atomics only, no floating-point
+ * accumulation anywhere): the result does not depend on the leaf size, the
+ * path (self order or bucketed), the host batch size, the grid or timing.
+ * NBKD_EINVAL before any device call, out_total untouched, with a message
+ * that names the function and the offending index: a NULL tree, q, edge array
+ * or out_total; mode or los out of range; n1 or n2 out of range; an edge that
+ * is NaN, infinite or negative, below its predecessor, or (mu) above 1;
+ * m >= 2^32.  m == 0 is NBKD_OK with out_total zeroed.
+ * The call returns when out_total is complete.  Host queries stream in batches
+ * (see above) with no per-query output; the totals accumulate over the
+ * batches and the thread's interrupt check runs between them.
+ * Out of scope: there are no per-query rows, no pair weights and no jackknife
+ * regions (a region's counts come from passing that region's points as the
+ * queries).
+ */
+#define NBKD_HIST2_RPPI 0      /* first axis rp (perpendicular), second axis pi (along the line of sight) */
+#define NBKD_HIST2_SMU  1      /* first axis s (= the tree's distance), second axis mu = pi / s */
+#define NBKD_MAX_LOS_BINS 64   /* second axis; the first axis keeps NBKD_MAX_RADII = 32 */
+nbkd_status nbkd_query_ball_hist2(const nbkd_tree *tree, const float *q, uint64_t m,
+                                  int32_t mode, int32_t los,
+                                  const float *edges1, int32_t n1,   /* host, ascending */
+                                  const float *edges2, int32_t n2,   /* host, ascending */
+                                  uint64_t *out_total,               /* (n1, n2) row-major, host */
+                                  uint32_t flags, void *stream);
+
+/*
  * NEW (no reference counterpart): friends-of-friends groups of the tree's own
  * points, the halo finder's first step.  Points i and j are friends iff
  * d2(i, j) <= b*b in float32, with d2 the tree's metric and b*b formed in
@@ -666,6 +729,13 @@ void nbkd_free(nbkd_tree *tree);
  *                      half-leaf boxes, staging loads at 32-bit offsets where
  *                      they fit); 0: the general instance that larger leaves
  *                      take.  Results never depend on it.
+ *   "hist2_flush_visits" 0 (default): a wave of nbkd_query_ball_hist2 adds its
+ *                      LDS histogram to the device totals at the end of its
+ *                      packet and before a 32-bit word could wrap; v > 0: also
+ *                      after every v leaf visits.  Results never depend on it.
+ *   "hist2_copies"     0 (default = 2): the interleaved LDS copies of that
+ *                      histogram per wave, rounded down to a power of two and
+ *                      to what 8 KiB holds.  Results never depend on it.
  * NEW (no reference counterpart: kdtree/src/cpp/pybind.cpp:196-216 has no knobs). */
 nbkd_status nbkd_set_tuning(const char *name, double value);
 nbkd_status nbkd_get_tuning(const char *name, double *value);

@@ -33,8 +33,9 @@ ARCH = os.environ.get("NBKD_ARCH", "gfx950")
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-Wall", "-Wno-unused-function", "-Wno-unused-const-variable"]
 SOURCES = ["api.cpp", "build.hip", "query.hip", "knn_collect.hip", "ball.hip", "ball_hist.hip",
-           "ball_sum.hip", "ball_profile.hip", "gravity.hip", "gravity_ewald.hip", "fof.hip",
-           "group.hip", "group_potential.hip", "slab.hip", "deposit.hip"]
+           "ball_hist2.hip", "ball_sum.hip", "ball_profile.hip", "gravity.hip",
+           "gravity_ewald.hip", "fof.hip", "group.hip", "group_potential.hip", "slab.hip",
+           "deposit.hip"]
 HEADERS = [os.path.join(CSRC, "internal.hpp"), os.path.join(CSRC, "metric.hpp"),
            os.path.join(CSRC, "packet.hpp"), os.path.join(CSRC, "gravity_dev.hpp"),
            os.path.join(ROOT, "include", "nbkd.h")]

@@ -25,6 +25,9 @@ NBKD_SORTED = 0x10
 KERNEL_TOPHAT, KERNEL_CUBIC, KERNEL_WENDLAND = 0, 1, 2
 NBKD_MAX_VALUES = 4
 NBKD_MAX_RADII = 32
+# nbkd_query_ball_hist2 modes and the second axis' bin limit
+NBKD_HIST2_RPPI, NBKD_HIST2_SMU = 0, 1
+NBKD_MAX_LOS_BINS = 64
 NBKD_EWALD_N = 64
 
 NODE_DTYPE = np.dtype([("dim", "<i4"), ("split", "<f4"), ("left", "<u4"), ("right", "<u4")])
@@ -51,6 +54,8 @@ _PROTOS = {
     "nbkd_query_kth": (_i32, [_c_p, _c_p, _u64, _i32, _c_p, _u32, _c_p]),
     "nbkd_query_ball_count": (_i32, [_c_p, _c_p, _u64, ctypes.c_float, _c_p, _u32, _c_p]),
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
+    "nbkd_query_ball_hist2": (_i32, [_c_p, _c_p, _u64, _i32, _i32, _c_p, _i32, _c_p, _i32, _c_p,
+                                     _u32, _c_p]),
     "nbkd_query_ball_sum": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _u32,
                                    _c_p]),
     "nbkd_query_ball_profile": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _c_p, _i32, _c_p, _u32,
@@ -114,7 +119,7 @@ def header_symbols() -> list[str]:
     """Function names declared in include/nbkd.h."""
     txt = open(HEADER).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(nbkd_[a-z_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(nbkd_[a-z0-9_]+)\s*\(", txt)))
 
 
 _lib = None
@@ -273,6 +278,29 @@ class Tree:
         _check(lib().nbkd_query_ball_hist(self.h, q_ptr, int(m), r.ctypes.data, r.shape[0],
                                           out_ptr, t.ctypes.data if total else None,
                                           NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE, stream))
+        return t
+
+    def ball_hist2(self, q, edges1, edges2, mode, los=2):
+        """nbkd_query_ball_hist2 of host queries: the (n1, n2) uint64 pair counts,
+        (rp, pi) bins for NBKD_HIST2_RPPI, (s, mu) bins for NBKD_HIST2_SMU."""
+        q = _host_f32(q).reshape(-1, 3)
+        e1 = _host_f32(edges1).reshape(-1)
+        e2 = _host_f32(edges2).reshape(-1)
+        t = np.empty((e1.shape[0], e2.shape[0]), np.uint64)
+        _check(lib().nbkd_query_ball_hist2(self.h, q.ctypes.data, q.shape[0], int(mode), int(los),
+                                           e1.ctypes.data, e1.shape[0], e2.ctypes.data,
+                                           e2.shape[0], t.ctypes.data, 0, None))
+        return t
+
+    def ball_hist2_device(self, q_ptr, m, edges1, edges2, mode, los=2, stream=None):
+        """Device queries; returns the (n1, n2) uint64 pair counts (the call
+        waits for them)."""
+        e1 = _host_f32(edges1).reshape(-1)
+        e2 = _host_f32(edges2).reshape(-1)
+        t = np.empty((e1.shape[0], e2.shape[0]), np.uint64)
+        _check(lib().nbkd_query_ball_hist2(self.h, q_ptr, int(m), int(mode), int(los),
+                                           e1.ctypes.data, e1.shape[0], e2.ctypes.data,
+                                           e2.shape[0], t.ctypes.data, NBKD_INPUT_DEVICE, stream))
         return t
 
     def ball_sum(self, q, h, values=None, kernel=1, count=False):

@@ -269,10 +269,12 @@ void tree_free(void *p) {
 
 namespace {
 // nbkd_set_tuning knobs (process-wide); defaults are the measured optima
-std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0}, {0.0}, {0.0}, {1.0}};
+std::atomic<double> g_tune[TUNE_N] = {{3.0}, {0.0}, {0.0}, {0.0}, {1.0},
+                                      {0.0}, {0.0}, {1.0}, {0.0}, {0.0}};
 const char *const g_tune_names[TUNE_N] = {"knn_seed_margin", "candidate_bytes", "host_batch",
                                           "host_threads", "self_order", "pinned_bytes",
-                                          "collect_wide_addr", "collect_one_chunk"};
+                                          "collect_wide_addr", "collect_one_chunk",
+                                          "hist2_flush_visits", "hist2_copies"};
 thread_local nbkd_interrupt_fn t_intr = nullptr;
 thread_local void *t_intr_user = nullptr;
 } // namespace
@@ -641,6 +643,68 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
     DeviceGuard g(tree->t.device);
     return query_ball_hist(tree->t, q, m, radii, nr, out_counts, out_total, flags,
                            (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
+// one axis of nbkd_query_ball_hist2's edges: false with the error set
+static bool hist2_edges_ok(const char *name, const float *e, int32_t n, int32_t nmax, bool mu) {
+    const std::string fn = "nbkd_query_ball_hist2: ";
+    if (n < 1 || n > nmax) {
+        set_error(fn + "the number of " + name + " edges must be in [1, " + std::to_string(nmax) +
+                  "], got " + std::to_string(n));
+        return false;
+    }
+    for (int32_t j = 0; j < n; ++j) {
+        if (!(e[j] >= 0.0f) || !(e[j] <= FLT_MAX)) {
+            set_error(fn + name + " edge " + std::to_string(j) + " is NaN, infinite or negative");
+            return false;
+        }
+        if (mu && e[j] > 1.0f) {
+            set_error(fn + name + " edge " + std::to_string(j) + " is above 1 (a mu edge)");
+            return false;
+        }
+        if (j > 0 && e[j] < e[j - 1]) {
+            set_error(fn + "the " + name + " edges must be ascending (edge " + std::to_string(j) +
+                      " is below edge " + std::to_string(j - 1) + ")");
+            return false;
+        }
+    }
+    return true;
+}
+
+nbkd_status nbkd_query_ball_hist2(const nbkd_tree *tree, const float *q, uint64_t m, int32_t mode,
+                                  int32_t los, const float *edges1, int32_t n1,
+                                  const float *edges2, int32_t n2, uint64_t *out_total,
+                                  uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    if (!tree || !q || !edges1 || !edges2 || !out_total) {
+        set_error("nbkd_query_ball_hist2: NULL argument (tree, q, edges1, edges2 or out_total)");
+        return NBKD_EINVAL;
+    }
+    if (mode != NBKD_HIST2_RPPI && mode != NBKD_HIST2_SMU) {
+        set_error("nbkd_query_ball_hist2: unknown mode " + std::to_string(mode));
+        return NBKD_EINVAL;
+    }
+    if (los < 0 || los > 2) {
+        set_error("nbkd_query_ball_hist2: the line of sight los must be 0, 1 or 2, got " +
+                  std::to_string(los));
+        return NBKD_EINVAL;
+    }
+    if (!hist2_edges_ok("first-axis", edges1, n1, NBKD_MAX_RADII, false) ||
+        !hist2_edges_ok("second-axis", edges2, n2, NBKD_MAX_LOS_BINS, mode == NBKD_HIST2_SMU))
+        return NBKD_EINVAL;
+    if (m >= (1ull << 32)) {
+        set_error("nbkd_query_ball_hist2: more than 2^32 - 1 queries per call are not supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) {
+        std::fill(out_total, out_total + (size_t)n1 * n2, (uint64_t)0);
+        return NBKD_OK;
+    }
+    DeviceGuard g(tree->t.device);
+    return query_ball_hist2(tree->t, q, m, mode, los, edges1, n1, edges2, n2, out_total, flags,
+                            (hipStream_t)stream);
     NBKD_GUARD_END
 }
 

@@ -23,6 +23,8 @@ enum WsSlot {
     WS_Q = 0, WS_KEYS, WS_KEYS2, WS_ORDER, WS_TMP, WS_HIST, WS_SUMS, WS_OUTD, WS_OUTI,
     WS_COUNT, WS_OFF, WS_IDX, WS_STATS, WS_LIST, WS_LT, WS_TG, WS_CAND, WS_CCOUNT,
     WS_LIST2, WS_RSORT, WS_KTHD, WS_KTHI, WS_KB, WS_ANCH, WS_PAIR, WS_HTOT,
+    // nbkd_query_ball_hist2: the (n1, n2) device totals
+    WS_H2TOT,
     // nbkd_query_ball_sum: the values in tree order, the uploaded host values,
     // a host batch's radii
     WS_VT, WS_VALS, WS_HRAD,
@@ -237,6 +239,8 @@ enum TuneId {
     TUNE_PINNED_BYTES,
     TUNE_COLLECT_WIDE,
     TUNE_COLLECT_ONE,
+    TUNE_HIST2_FLUSH,
+    TUNE_HIST2_COPIES,
     TUNE_N
 };
 // host memcpy split over the library's copy threads (api.cpp): the host-buffer
@@ -440,6 +444,33 @@ void launch_ball_hist_outside_dev(const Tree &t, const float *q, const uint32_t 
                                   uint32_t *out_counts, unsigned long long *totals,
                                   hipStream_t s);
 
+// ball_hist2.hip: the anisotropic pair counts.  thr.t1[0 .. n1) and
+// thr.t2[0 .. n2) = the ascending squared edges of the two axes (passed to the
+// kernels by value); totals = n1 * n2 row-major counters the pairs are added
+// to.  par.rshift = log2 of the interleaved LDS histogram copies per wave
+// (hist2_copies_shift: the largest power of two <= copies, 0 = the default,
+// that keeps n1 * n2 copies within HIST2_LDS_WORDS); par.bound is filled in by
+// the launch.  Periodic queries outside [0, L]^3 are skipped by the packet
+// kernel and answered by the second launch (list length in device memory).
+constexpr uint32_t HIST2_LDS_WORDS = NBKD_MAX_RADII * NBKD_MAX_LOS_BINS; // 8 KiB per wave
+constexpr int HIST2_DEFAULT_COPIES = 2; // measured: DESIGN.md section 3
+struct Hist2Thr {
+    float t1[NBKD_MAX_RADII];
+    float t2[NBKD_MAX_LOS_BINS];
+};
+struct Hist2Par {
+    int n1, n2, mode, los, rshift;
+    uint32_t flush_visits; // flush the wave's histogram every so many leaf visits (0: wrap bound)
+    float bound;           // the walk's bound on d2
+};
+int hist2_copies_shift(int nbins, int copies);
+void launch_ball_hist2(const Tree &t, const float *q, const uint32_t *order, uint32_t m,
+                       const Hist2Thr &thr, Hist2Par par, unsigned long long *totals,
+                       hipStream_t s);
+void launch_ball_hist2_outside_dev(const Tree &t, const float *q, const uint32_t *list,
+                                   const uint32_t *nout, const Hist2Thr &thr, Hist2Par par,
+                                   unsigned long long *totals, hipStream_t s);
+
 // ball_sum.hip: kernel-weighted sums over per-query balls (nbkd_query_ball_sum).
 // vt[p, c] = values[row(p), c] for tree positions p < n8 (values == nullptr: 1;
 // padding positions: 0), row(p) from the build's permutation
@@ -516,6 +547,12 @@ nbkd_status query_ball_csr(const Tree &t, const float *q, uint64_t m, float r, u
 nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const float *radii, int nr,
                             uint32_t *out_counts, uint64_t *out_total, uint32_t flags,
                             hipStream_t s);
+
+// edges1 / edges2: n1 / n2 ascending, finite, non-negative (SMU: edges2 <= 1);
+// mode, los, m < 2^32 and the NULL cases checked by the caller (api.cpp)
+nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode, int los,
+                             const float *edges1, int n1, const float *edges2, int n2,
+                             uint64_t *out_total, uint32_t flags, hipStream_t s);
 
 // h, values: on q's side; nv, kernel and the NULL cases checked by the caller
 // (api.cpp); m > 0

@@ -91,6 +91,37 @@ __device__ __forceinline__ float point_d2_fast(float qx, float qy, float qz, flo
     return (a + b) + c;
 }
 
+// The three per-axis squares that point_d2 / point_d2_fast add up, one by one
+// (ball_hist2.hip classifies a pair on them): (ax + ay) + az is that d2, bit
+// for bit.
+template <bool PER>
+__device__ __forceinline__ void point_axes(float qx, float qy, float qz, float px, float py,
+                                           float pz, float L, float &ax, float &ay, float &az) {
+    float dx = px - qx, dy = py - qy, dz = pz - qz;
+    if constexpr (PER) {
+        dx = fminf(fminf(fabsf(dx), fabsf(dx - L)), fabsf(dx + L));
+        dy = fminf(fminf(fabsf(dy), fabsf(dy - L)), fabsf(dy + L));
+        dz = fminf(fminf(fabsf(dz), fabsf(dz - L)), fabsf(dz + L));
+    }
+    ax = dx * dx;
+    ay = dy * dy;
+    az = dz * dz;
+}
+template <bool PER>
+__device__ __forceinline__ void point_axes_fast(float qx, float qy, float qz, float px, float py,
+                                                float pz, float L, float &ax, float &ay,
+                                                float &az) {
+    float dx = px - qx, dy = py - qy, dz = pz - qz;
+    if constexpr (PER) {
+        dx = fminf(fabsf(dx), L - fabsf(dx));
+        dy = fminf(fabsf(dy), L - fabsf(dy));
+        dz = fminf(fabsf(dz), L - fabsf(dz));
+    }
+    ax = dx * dx;
+    ay = dy * dy;
+    az = dz * dz;
+}
+
 // Lower bound of the squared distance from q to any point of the box, for the
 // packet kernels' pruning (not the reference's box_distance, whose exact bits
 // only the reference-exact kernel needs).  Per axis, a = lo - q, b = q - hi:

@@ -2197,6 +2197,88 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
     return NBKD_OK;
 }
 
+// the anisotropic pair counts of m device queries, added to the device
+// counters tot
+static nbkd_status hist2_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
+                                const Hist2Thr &thr, const Hist2Par &par,
+                                unsigned long long *tot, uint32_t flags, hipStream_t s) {
+    if (m == 0) return NBKD_OK;
+    const uint32_t mm = (uint32_t)m;
+    const float *dq = nullptr;
+    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
+    if (rc) return rc;
+    uint32_t *ord = nullptr;
+    rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
+                                    : sort_queries(t, ws, dq, mm, ord, s);
+    if (rc) return rc;
+    // periodic queries outside [0, L]^3: listed (the length stays in device
+    // memory), every point tested for them
+    uint32_t *list = nullptr;
+    if (t.periodic) {
+        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
+        if (!list) return NBKD_ENOMEM;
+        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
+        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
+    }
+    TimedScope ts("ball_hist2", s);
+    launch_ball_hist2(t, dq, ord, mm, thr, par, tot, s);
+    if (list) launch_ball_hist2_outside_dev(t, dq, list, list + mm, thr, par, tot, s);
+    NBKD_HIP(hipGetLastError());
+    return NBKD_OK;
+}
+
+nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode, int los,
+                             const float *edges1, int n1, const float *edges2, int n2,
+                             uint64_t *out_total, uint32_t flags, hipStream_t s) {
+    const size_t nbins = (size_t)n1 * n2;
+    std::fill(out_total, out_total + nbins, (uint64_t)0);
+    if (m == 0 || t.n == 0 || t.nnodes == 0) return NBKD_OK;
+    // the thresholds, ball_common's expression per edge (a product that
+    // overflows counts as FLT_MAX); they travel to the kernels by value (no
+    // host-to-device copy whose source could go away)
+    Hist2Thr thr;
+    for (int j = 0; j < NBKD_MAX_RADII; ++j) {
+        const float e = edges1[std::min(j, n1 - 1)];
+        thr.t1[j] = std::min(e * e, FLT_MAX);
+    }
+    for (int j = 0; j < NBKD_MAX_LOS_BINS; ++j) {
+        const float e = edges2[std::min(j, n2 - 1)];
+        thr.t2[j] = std::min(e * e, FLT_MAX);
+    }
+    Hist2Par par;
+    par.n1 = n1;
+    par.n2 = n2;
+    par.mode = mode;
+    par.los = los;
+    par.rshift = hist2_copies_shift((int)nbins, (int)std::min(tuning(TUNE_HIST2_COPIES), 64.0));
+    par.flush_visits = (uint32_t)std::min(tuning(TUNE_HIST2_FLUSH), 4294967295.0);
+    par.bound = 0.0f;
+    Workspace &ws = acquire_ws(t);
+    WsCall call(ws, s, std::adopt_lock);
+    NBKD_HIP(call.err);
+    unsigned long long *tot = (unsigned long long *)ws.get(WS_H2TOT, nbins * 8, s);
+    if (!tot) return NBKD_ENOMEM;
+    NBKD_HIP(hipMemsetAsync(tot, 0, nbins * 8, s));
+    // nothing leaves the device but the totals
+    flags |= NBKD_OUTPUT_DEVICE;
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    nbkd_status rc;
+    if ((flags & dev_io) == dev_io) {
+        rc = hist2_common(t, ws, q, m, thr, par, tot, flags, s);
+    } else {
+        rc = host_pipeline(ws, q, m, flags, 0, nullptr, nullptr, 40,
+                           [&](const float *dq, uint64_t nb, void *const *, hipStream_t st) {
+                               return hist2_common(t, ws, dq, nb, thr, par, tot, flags | dev_io,
+                                                   st);
+                           }, s);
+    }
+    if (rc) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
+    NBKD_HIP(hipMemcpyAsync(out_total, tot, nbins * 8, hipMemcpyDeviceToHost, s));
+    NBKD_HIP(hipStreamSynchronize(s));
+    return NBKD_OK;
+}
+
 namespace {
 
 // The CSR fill of one batch: nb device queries, their rows at the device

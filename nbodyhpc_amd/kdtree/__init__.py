@@ -9,7 +9,10 @@ extension or without a GPU the constructor raises.
 
 Additions (no reference counterpart): ``query_ball`` (scipy-style radius
 query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
-many radii in one tree walk), ``fof`` / ``fof_labels`` (friends-of-friends
+many radii in one tree walk), ``count_pairs_rppi`` / ``count_pairs_smu`` /
+``pair_counts_rppi`` / ``pair_counts_smu`` / ``xi_rppi`` / ``xi_smu``
+(anisotropic pair counts about a line of sight in one tree walk, wp(rp) and
+the multipoles from them), ``fof`` / ``fof_labels`` (friends-of-friends
 groups of the tree's points), ``fof_catalog`` (members, mass, centre, extent
 and value moments per group, reduced on the GPU), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
@@ -54,6 +57,8 @@ _KERNELS = {"tophat": (0, 3.0 / (4.0 * math.pi)), "cubic": (1, 8.0 / math.pi),
             "wendland": (2, 21.0 / (2.0 * math.pi))}
 _MAX_VALUES = 4  # NBKD_MAX_VALUES
 _MAX_RADII = 32  # NBKD_MAX_RADII
+_MAX_LOS_BINS = 64  # NBKD_MAX_LOS_BINS
+_HIST2_RPPI, _HIST2_SMU = 0, 1  # NBKD_HIST2_*
 
 
 def _flatten(points):
@@ -187,6 +192,140 @@ class KDTree(cKDTree):
         if np.ndim(r) == 0:
             return (total - n) // 2
         return (total - np.uint64(n)) // np.uint64(2)
+
+    @staticmethod
+    def _edges(e, name, nmax, mu=False):
+        """the float32 edges of one axis of the anisotropic counts, checked"""
+        e = np.asarray(e, dtype=np.float32)
+        if e.ndim != 1:
+            raise ValueError(f"{name} must be a 1-D array of edges")
+        if e.size == 0:
+            raise ValueError(f"{name} is empty: at least one edge is needed")
+        if e.size > nmax:
+            raise ValueError(f"{name} holds {e.size} edges: at most {nmax} per call")
+        if not np.all(np.isfinite(e)) or np.any(e < 0):
+            raise ValueError(f"every edge of {name} must be finite and >= 0")
+        if mu and np.any(e > 1):
+            raise ValueError(f"every edge of {name} must be <= 1")
+        if np.any(e[1:] < e[:-1]):
+            raise ValueError(f"{name} must be ascending (non-decreasing)")
+        return np.ascontiguousarray(e)
+
+    def _count_pairs2(self, points, e1, e2, mode, los, names):
+        e1 = self._edges(e1, names[0], _MAX_RADII)
+        e2 = self._edges(e2, names[1], _MAX_LOS_BINS, mu=mode == _HIST2_SMU)
+        if los not in (0, 1, 2):
+            raise ValueError("los must be 0, 1 or 2 (the axis of the line of sight)")
+        points, _ = _flatten(points)
+        return super().query_ball_hist2(points, e1, e2, mode, int(los))
+
+    def count_pairs_rppi(self, points: np.ndarray, rp, pi, los: int = 2):
+        """Pair counts of ``points`` against the tree's points in (rp, pi) bins,
+        one tree walk: uint64 (len(rp), len(pi)).  rp (up to 32) and pi (up to
+        64) are ascending edges, each finite and >= 0; ``los`` is the axis of the
+        line of sight.  With a = the per-axis squared separations (float32,
+        minimum image on a periodic tree), pi2 = a[los], rp2 = the sum of the
+        other two, a pair falls into bin (#{k: rp2 > rp[k]^2}, #{l: pi2 >
+        pi[l]^2}) and is dropped when either index runs past the last edge: bins
+        are differential on both axes, bin 0 reaches from 0 to the first edge.
+        Cross counts D1D2, DR and RR come from passing the other catalogue."""
+        return self._count_pairs2(points, rp, pi, _HIST2_RPPI, los, ("rp", "pi"))
+
+    def count_pairs_smu(self, points: np.ndarray, s, mu, los: int = 2):
+        """Pair counts of ``points`` against the tree's points in (s, mu) bins,
+        one tree walk: uint64 (len(s), len(mu)).  s (up to 32 edges) bins the
+        tree's own distance (s2 = d2 of ``count_neighbors``), mu (up to 64 edges
+        in [0, 1]) bins |pi| / s through pi2 <= fl(mu[l]^2 * s2).  With a last mu
+        edge of 1 every pair within s[-1] is counted, and the sum over mu equals
+        ``count_neighbors(points, s, cumulative=False)``."""
+        return self._count_pairs2(points, s, mu, _HIST2_SMU, los, ("s", "mu"))
+
+    def _auto2(self, counts):
+        """ordered counts of the tree's own points -> unordered pairs: the n
+        self pairs leave bin (0, 0), every bin is halved"""
+        counts = counts.copy()
+        counts[0, 0] -= np.uint64(self._n_input)
+        return counts // np.uint64(2)
+
+    def pair_counts_rppi(self, rp, pi, los: int = 2):
+        """Auto pair counts DD(rp, pi) of the tree's own points: unordered pairs
+        i < j per bin (``count_pairs_rppi``'s bins), self pairs removed."""
+        return self._auto2(self.count_pairs_rppi(self.points(), rp, pi, los))
+
+    def pair_counts_smu(self, s, mu, los: int = 2):
+        """Auto pair counts DD(s, mu) of the tree's own points: unordered pairs
+        i < j per bin (``count_pairs_smu``'s bins), self pairs removed."""
+        return self._auto2(self.count_pairs_smu(self.points(), s, mu, los))
+
+    def _xi_args(self, edges, name, nsec, nsec_name):
+        if not self.periodic:
+            raise ValueError("the natural estimator with analytic RR needs a periodic tree")
+        e = self._edges(edges, name, _MAX_RADII)
+        if e.size < 2:
+            raise ValueError(f"{name} needs at least two edges (one bin)")
+        if np.any(e[1:] <= e[:-1]):
+            raise ValueError(f"{name} must be strictly ascending")
+        if int(nsec) != nsec or not 1 <= nsec <= _MAX_LOS_BINS:
+            raise ValueError(f"{nsec_name} must be an integer in [1, {_MAX_LOS_BINS}]")
+        return e, int(nsec)
+
+    def xi_rppi(self, rp_edges, pi_max: float, npi: int, los: int = 2):
+        """xi(rp, pi) and wp(rp) of the tree's own points on a periodic tree:
+        the natural estimator DD / RR - 1 with analytic RR, in float64.
+
+        rp_edges : n strictly ascending edges (n - 1 bins; what lies inside the
+            first edge, the self pairs among it, is dropped); rp_edges[-1] <= L/2.
+        pi_max, npi : npi equal bins of |pi| up to pi_max <= L/2 (edges
+            pi_max (l + 1) / npi, rounded to float32).
+        Returns (xi (n - 1, npi), wp (n - 1,)), wp = 2 sum_l xi dpi.  RR per
+        ordered pair is N (N / L^3) pi (rp_hi^2 - rp_lo^2) 2 (pi_hi - pi_lo), with
+        the float32 edges the counts used."""
+        e, npi = self._xi_args(rp_edges, "rp_edges", npi, "npi")
+        L = float(self.boxsize)
+        if not (math.isfinite(pi_max) and pi_max > 0):
+            raise ValueError("pi_max must be finite and > 0")
+        if float(e[-1]) > 0.5 * L or pi_max > 0.5 * L:
+            raise ValueError("rp_edges[-1] and pi_max must not exceed half the box")
+        pe = (float(pi_max) * (np.arange(npi, dtype=np.float64) + 1.0) / npi).astype(np.float32)
+        dd = self.count_pairs_rppi(self.points(), e, pe, los)[1:].astype(np.float64)
+        n = float(self._n_input)
+        r = e.astype(np.float64)
+        p = np.concatenate([[0.0], pe.astype(np.float64)])
+        vol = math.pi * (r[1:] ** 2 - r[:-1] ** 2)[:, None] * 2.0 * (p[1:] - p[:-1])[None, :]
+        xi = dd / (n * (n / L ** 3) * vol) - 1.0
+        wp = 2.0 * (xi * (p[1:] - p[:-1])[None, :]).sum(axis=1)
+        return xi, wp
+
+    def xi_smu(self, s_edges, nmu: int, ells=(0, 2, 4), los: int = 2):
+        """xi(s, mu) and its multipoles of the tree's own points on a periodic
+        tree: the natural estimator DD / RR - 1 with analytic RR, in float64.
+
+        s_edges : n strictly ascending edges (n - 1 bins; what lies inside the
+            first edge is dropped); s_edges[-1] <= L/2.
+        nmu : equal bins of mu in [0, 1] (edges (l + 1) / nmu, rounded to float32).
+        Returns (xi (n - 1, nmu), multipoles {ell: (n - 1,)}), xi_ell(s) =
+        (2 ell + 1) sum_l xi P_ell(mu_mid) dmu.  RR per ordered pair is
+        N (N / L^3) (4 pi / 3) (s_hi^3 - s_lo^3) (mu_hi - mu_lo)."""
+        e, nmu = self._xi_args(s_edges, "s_edges", nmu, "nmu")
+        L = float(self.boxsize)
+        if float(e[-1]) > 0.5 * L:
+            raise ValueError("s_edges[-1] must not exceed half the box")
+        me = ((np.arange(nmu, dtype=np.float64) + 1.0) / nmu).astype(np.float32)
+        dd = self.count_pairs_smu(self.points(), e, me, los)[1:].astype(np.float64)
+        n = float(self._n_input)
+        r = e.astype(np.float64)
+        u = np.concatenate([[0.0], me.astype(np.float64)])
+        dmu = u[1:] - u[:-1]
+        vol = (4.0 * math.pi / 3.0) * (r[1:] ** 3 - r[:-1] ** 3)[:, None] * dmu[None, :]
+        xi = dd / (n * (n / L ** 3) * vol) - 1.0
+        mid = 0.5 * (u[1:] + u[:-1])
+        poles = {}
+        for ell in ells:
+            c = np.zeros(int(ell) + 1)
+            c[int(ell)] = 1.0
+            leg = np.polynomial.legendre.legval(mid, c)
+            poles[int(ell)] = (2 * int(ell) + 1) * (xi * (leg * dmu)[None, :]).sum(axis=1)
+        return xi, poles
 
     def fof(self, linking_length: float, min_members: int = 1, return_sizes: bool = False):
         """Friends-of-friends groups of the tree's own points: two points are
