@@ -136,6 +136,26 @@ nbkd_status nbkd_query_kth(const nbkd_tree *tree, const float *q, uint64_t m, in
 /*
  * NEW (no reference counterpart): number of points with d2 <= r*r of each
  * query (periodic metric when the tree is periodic).  out_count is (m,) uint32.
+ * The radius contract, shared by nbkd_query_ball_csr, nbkd_query_ball_hist
+ * and nbkd_fof (and, per edge, by nbkd_query_ball_sum, _profile and _hist2):
+ * the threshold is T = min(fl(r*r), FLT_MAX), the product formed in float32,
+ * and a point is inside iff d2 <= T in float32.
+ *   - a negative r acts as |r|; r = 0 (and any r whose square underflows to
+ *     0) reaches coincident points only;
+ *   - r = NaN matches nothing (T is NaN);
+ *   - r = +-inf, or any r whose square overflows (|r| >= 1.8447e19), reaches
+ *     exactly the points whose d2 is finite;
+ *   - padding points are in no ball for every r;
+ *   - a query with a NaN coordinate has an empty ball (an empty row, all-zero
+ *     bins), and so has a query whose d2 to every point overflows (an
+ *     infinite coordinate, or one of about 1.8e19 and beyond).  Such a query
+ *     changes nothing in the results of the other queries of the call.
+ * The same queries in nbkd_query_knn and nbkd_query_kth give the reference's
+ * row for a query that finds nothing: all (sqrtf(FLT_MAX), 0xFFFFFFFF), or
+ * FLT_MAX with NBKD_SQUARED.
+ * Out of scope (unspecified values, untested): non-finite point coordinates
+ * at build time, and non-finite queries to nbkd_gravity and nbkd_group_*
+ * (nbkd_gravity_ewald defines its own rule).
  */
 nbkd_status nbkd_query_ball_count(const nbkd_tree *tree, const float *q, uint64_t m, float r,
                                   uint32_t *out_count, uint32_t flags, void *stream);
@@ -148,8 +168,12 @@ nbkd_status nbkd_query_ball_count(const nbkd_tree *tree, const float *q, uint64_
  * neighbours allowed), each finite and >= 0, 1 <= nr <= NBKD_MAX_RADII.  The
  * count of query i at radius j is the number of points with d2 <= r[j]*r[j]
  * (float32, the tree's metric): column j of out_counts equals
- * nbkd_query_ball_count(q, r[j]) bit for bit.  Counts are cumulative in j;
- * per-bin counts are their differences.
+ * nbkd_query_ball_count(q, r[j]) bit for bit, under that call's radius
+ * contract: the threshold is min(fl(r[j]*r[j]), FLT_MAX), so a radius whose
+ * square overflows counts the points at a finite d2 and never a padding
+ * point, and a query with a NaN coordinate or with every d2 = inf has an
+ * all-zero row.  Counts are cumulative in j; per-bin counts are their
+ * differences.
  *   out_counts  (m, nr) row-major uint32, host or device memory
  *               (NBKD_OUTPUT_DEVICE), or NULL
  *   out_total   (nr,) uint64, always host memory, or NULL: the sum of column j
@@ -236,7 +260,10 @@ nbkd_status nbkd_query_ball_hist2(const nbkd_tree *tree, const float *q, uint64_
  * (((dx^2 + dy^2) + dz^2), per-axis minimum image on a periodic tree).  Groups
  * are the connected components of the friendship graph; a point without a
  * friend is a group of one.  b == 0 is valid (only coincident points link); b
- * NaN, infinite or negative is NBKD_EINVAL.
+ * NaN, infinite or negative is NBKD_EINVAL.  The threshold follows
+ * nbkd_query_ball_count's radius contract, min(fl(b*b), FLT_MAX): a finite b
+ * whose square overflows links every pair of real points (one group) and no
+ * padding point.
  *   out_label   (n,) uint32, required: out_label[i] = the smallest input row of
  *               i's group.  Labels are input rows 0..n-1 (the build's
  *               permutation), also after nbkd_set_ids replaced the ids.  The
@@ -673,6 +700,11 @@ nbkd_status nbkd_group_potential(const nbkd_tree *tree,
  * each row in tree traversal order, or ascending with NBKD_SORTED (a per-row
  * sort on the device).  Call with out_idx == NULL first to get offsets[m]
  * (the required capacity), then again with a buffer of that size.
+ * The rows follow nbkd_query_ball_count's radius contract, and the counting
+ * pass and the fill see the same threshold min(fl(r*r), FLT_MAX): row i holds
+ * offsets[i + 1] - offsets[i] ids, each < n, for every r -- every point at a
+ * finite d2 when r*r overflows (r = inf included), none for r = NaN or for a
+ * query with a NaN coordinate.
  * Batched (round 6): the counts stream through the host-buffer pipeline; the
  * fill runs in batches of at most ~64 M ids (a row longer than that is a batch
  * of its own) whose ids are sorted and copied out while the next batch is

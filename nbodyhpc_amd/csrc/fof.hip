@@ -275,7 +275,7 @@ nbkd_status fof(const Tree &t, float b, uint32_t *out_label, uint32_t *out_size,
     if (out_ngroups) *out_ngroups = 0;
     if (t.n == 0) return NBKD_OK;
     const uint32_t n8 = (uint32_t)t.n8, n = (uint32_t)t.n; // n8 <= UINT32_MAX (build)
-    const float b2 = b * b;                                 // the count's threshold expression
+    const float b2 = radius_thr(b); // the count's threshold expression
     const bool dev_out = flags & NBKD_OUTPUT_DEVICE;
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);

@@ -101,6 +101,15 @@ struct WsCall {
     }
 };
 
+// The squared radius of the whole radius family (count, CSR, hist, FoF, and
+// the sum / profile / hist2 edges): fl(r * r) in float32, a product that
+// overflows counting as FLT_MAX, so the padding points and the filler lanes
+// (d2 = inf) pass no `d2 <= thr`.  A NaN stays NaN and matches nothing.
+inline float radius_thr(float r) {
+    const float r2 = r * r;
+    return r2 > FLT_MAX ? FLT_MAX : r2;
+}
+
 constexpr int NBKD_PAD_LEAVES = 8;
 constexpr int NBKD_GROUP = 8;   // points per sub-leaf group (leaf counts are multiples of 8)
 constexpr int NBKD_GBLOCK = 128; // points ordered together into groups (<= 64 lanes x 2)

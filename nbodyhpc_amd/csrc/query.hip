@@ -1762,7 +1762,7 @@ static nbkd_status ball_common(const Tree &t, Workspace &ws, const float *q, uin
     rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
                                     : sort_queries(t, ws, dq, mm, ord, s);
     if (rc) return rc;
-    const float r2 = r * r;
+    const float r2 = radius_thr(r);
     // periodic queries outside [0, L]^3: listed (their count stays in device
     // memory), every point tested for them
     uint32_t *list = nullptr;
@@ -2156,12 +2156,12 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
     }
     if (out_total) std::fill(out_total, out_total + nr, (uint64_t)0);
     if (m == 0) return NBKD_OK;
-    // the thresholds, ball_common's expression per radius; they travel to the
-    // kernels by value (no host-to-device copy whose source could go away)
+    // the thresholds, ball_common's expression per radius (radius_thr: a product
+    // that overflows counts as FLT_MAX); they travel to the kernels by value (no host-to-device copy whose source could go away)
     HistThr thr;
     for (int j = 0; j < NBKD_MAX_RADII; ++j) {
         const float r = radii[std::min(j, nr - 1)];
-        thr.t[j] = r * r;
+        thr.t[j] = radius_thr(r);
     }
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
@@ -2239,11 +2239,11 @@ nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode
     Hist2Thr thr;
     for (int j = 0; j < NBKD_MAX_RADII; ++j) {
         const float e = edges1[std::min(j, n1 - 1)];
-        thr.t1[j] = std::min(e * e, FLT_MAX);
+        thr.t1[j] = radius_thr(e);
     }
     for (int j = 0; j < NBKD_MAX_LOS_BINS; ++j) {
         const float e = edges2[std::min(j, n2 - 1)];
-        thr.t2[j] = std::min(e * e, FLT_MAX);
+        thr.t2[j] = radius_thr(e);
     }
     Hist2Par par;
     par.n1 = n1;
@@ -2289,7 +2289,7 @@ nbkd_status ball_fill_batch(const Tree &t, Workspace &ws, const float *dq, uint3
     nbkd_status rc = self_query(t, dq, nb, NBKD_INPUT_DEVICE) ? self_order(t, ws, nb, ord, s)
                                                                : sort_queries(t, ws, dq, nb, ord, s);
     if (rc) return rc;
-    const float r2 = r * r;
+    const float r2 = radius_thr(r);
     uint32_t *list = nullptr, nout = 0;
     if (t.periodic) { // periodic queries outside [0, L]^3: every point tested for them
         list = (uint32_t *)ws.get(WS_LIST, (size_t)nb * 8 + 16, s);

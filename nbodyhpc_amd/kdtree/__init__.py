@@ -118,6 +118,12 @@ class KDTree(cKDTree):
                    **kwargs):
         """Points within distance r (d2 <= r*r in float32, the kNN metric).
 
+        The threshold is min(fl(r*r), FLT_MAX): a negative r acts as |r|,
+        r = NaN matches nothing, and r = inf (or any r whose square overflows)
+        returns every point at a finite distance, never a padding point.  A
+        query with a NaN coordinate, or so far away that every d2 overflows,
+        gets an empty row (count 0).
+
         return_length=True -> uint32 counts, shape points.shape[:-1].
         return_csr=True -> (offsets uint64 (M + 1,), indices uint32): row i is
         indices[offsets[i]:offsets[i + 1]] (each row sorted on the device
@@ -152,7 +158,10 @@ class KDTree(cKDTree):
         r : a scalar or a 1-D ascending array of up to 32 radii (each finite
             and >= 0; equal neighbours allowed).  The count at radius r[j] is
             the number of tree points with d2 <= r[j]*r[j] in float32, the
-            value ``query_ball(points, r[j], return_length=True)`` gives.
+            value ``query_ball(points, r[j], return_length=True)`` gives
+            (threshold min(fl(r[j]*r[j]), FLT_MAX): a square that overflows
+            counts every point at a finite distance; a query with a NaN
+            coordinate or with every d2 = inf counts nothing).
         per_point=False -> uint64 totals over all queries, shape (nr,) (a
             scalar r: a Python int).
         per_point=True -> uint32 counts, shape points.shape[:-1] + (nr,) (a
@@ -331,7 +340,9 @@ class KDTree(cKDTree):
         """Friends-of-friends groups of the tree's own points: two points are
         friends when d2 <= linking_length**2 in float32 (the ``query_ball``
         predicate, periodic on a periodic tree), groups are the connected
-        components.
+        components.  The linking length must be finite and >= 0; one whose
+        square overflows in float32 (threshold min(fl(b*b), FLT_MAX)) links
+        every point into one group.
 
         Returns ``group``, int64 (N,): groups are numbered 0..G-1 by descending
         size, ties by the smaller first member (input row); points of groups

@@ -601,10 +601,19 @@ ORC_EXPORT int orc_knn_brute(const float *aos, int64_t n, int32_t periodic, floa
     return ORC_OK;
 }
 
-/* NEW (no reference): radius count, brute force.  d2 <= r*r, same d2 formula. */
+/* The squared radius of the radius counts: fl(r*r), an overflowing product
+ * counting as FLT_MAX (so a point at d2 = inf, a padding point included, is in
+ * no ball); a NaN stays NaN and matches nothing.  The library's radius_thr. */
+static float ball_thr(float r) {
+    float r2 = r * r;
+    return r2 > FLT_MAX ? FLT_MAX : r2;
+}
+
+/* NEW (no reference): radius count, brute force.  d2 <= ball_thr(r), same d2
+ * formula. */
 ORC_EXPORT int orc_ball_count_brute(const float *aos, int64_t n, int32_t periodic, float box,
                                     const float *q, int64_t m, float r, uint32_t *out_count) {
-    float r2 = r * r;
+    float r2 = ball_thr(r);
     for (int64_t j = 0; j < m; ++j) {
         const float *qq = q + 3 * j;
         uint32_t c = 0;
@@ -620,7 +629,7 @@ ORC_EXPORT int orc_ball_count_brute(const float *aos, int64_t n, int32_t periodi
 }
 
 /* NEW (no reference): radius count through the tree.  Same DFS, pruning by
- * box distance > r*r. Used as the CPU baseline of the ball path. */
+ * box distance > ball_thr(r). Used as the CPU baseline of the ball path. */
 static uint64_t g_ball_nodes, g_ball_points; /* orc_ball_count_stats (single thread) */
 
 static uint32_t ball_rec(const orc_tree *t, const orc_node *node, const float q[3], float bounds[6],
@@ -651,7 +660,7 @@ static uint32_t ball_rec(const orc_tree *t, const orc_node *node, const float q[
 
 ORC_EXPORT int orc_ball_count(const orc_tree *t, const float *q, int64_t m, float r,
                               uint32_t *out_count) {
-    float r2 = r * r;
+    float r2 = ball_thr(r);
     for (int64_t j = 0; j < m; ++j) {
         float bounds[6];
         for (int i = 0; i < 3; ++i) {
