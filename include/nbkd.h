@@ -253,6 +253,74 @@ nbkd_status nbkd_query_ball_hist2(const nbkd_tree *tree, const float *q, uint64_
                                   uint32_t flags, void *stream);
 
 /*
+ * NEW (no reference counterpart): nbkd_query_ball_hist2 in the observer frame,
+ * for light cones, cut-sky mocks and survey catalogues with their randoms: the
+ * line of sight of each pair runs from the observer through the pair's
+ * midpoint (the convention of Corrfunc's DDrppi_mocks / DDsmu_mocks), not
+ * along a coordinate axis.  DD, DR and RR for the Landy-Szalay estimator come
+ * from passing the data or the randoms as the queries of the data's or the
+ * randoms' tree.
+ *   observer   (3,) float32, host memory, each component finite
+ * The edges, the thresholds T1, T2 and M, the bin rule, the flags, the
+ * streaming of host queries, the interrupt check, m == 0 and "returns when
+ * out_total is complete" are those of nbkd_query_ball_hist2, word for word.
+ * Only the two coordinates of a pair change.  All of it is float32 without
+ * fused multiply-adds, every division IEEE correctly rounded (denormals
+ * included).  For query i (position q), tree point j (position p), observer o,
+ * per axis a:
+ *   s_a  = fl(p_a - q_a)
+ *   s2   = fl(fl(s_x*s_x + s_y*s_y) + s_z*s_z)     the d2 of nbkd_query_ball_count,
+ *                                                  bit for bit
+ *   l_a  = fl(fl(p_a - o_a) + fl(q_a - o_a))       twice the midpoint's offset from
+ *                                                  the observer
+ *   dot  = fl(fl(fl(s_x*l_x) + fl(s_y*l_y)) + fl(s_z*l_z))
+ *   l2   = fl(fl(fl(l_x*l_x) + fl(l_y*l_y)) + fl(l_z*l_z))
+ *   x    = fl(dot*dot)
+ *   pi2  = l2 > 0 ? fminf(fl(x / l2), s2) : 0      the clamp makes pi2 <= s2 hold in
+ *                                                  float32 (fminf: s2 where the
+ *                                                  quotient is NaN)
+ *   rp2  = fl(s2 - pi2)                            >= 0 by the clamp
+ * Bins, with T1, T2 and M formed as in nbkd_query_ball_hist2:
+ *   RPPI  b1 = #{k : !(rp2 <= T1[k])},  b2 = #{l : !(pi2 <= T2[l])}
+ *   SMU   b1 = #{k : !(s2 <= T1[k])};  if b1 < n1,
+ *         b2 = #{l : !(pi2 <= fl(M[l] * s2))}
+ * The pair adds 1 to out_total[b1, b2] iff b1 < n1 and b2 < n2.  Consequences:
+ *   - the ordered pairs (i, j) and (j, i) fall into the same bin: s negates
+ *     exactly, l is a commutative sum, so dot negates exactly and x is
+ *     unchanged.  Every bin of an auto count is therefore even once the n self
+ *     pairs leave bin (0, 0);
+ *   - a pair with s2 == 0 is in bin (0, 0);
+ *   - with a last mu edge of exactly 1 every pair with b1 < n1 is counted, and
+ *     the row sums equal the first difference of nbkd_query_ball_hist's totals
+ *     at edges1;
+ *   - l2 == 0 is defined as pi2 = 0: both points at the observer, or the two
+ *     points mirror images about it;
+ *   - padding points are in no bin;
+ *   - a query with a NaN coordinate, or with every s2 infinite, is in no bin
+ *     and changes nothing for the others;
+ *   - x = fl(dot*dot) overflows once |s| |l| passes 2^64 (about 1.8e19): the
+ *     quotient is then infinite and the clamp gives pi2 = s2, rp2 = 0.  Keep
+ *     the product of the separation and the distance below that.
+ * NBKD_EINVAL before any device call, out_total untouched, with a message that
+ * names nbkd_query_ball_hist2_obs and the offending index: every condition of
+ * nbkd_query_ball_hist2 except los; observer == NULL; an observer component
+ * that is NaN or infinite.  After those checks (and after m == 0, which is
+ * NBKD_OK with out_total zeroed) the handle is read: a periodic tree is
+ * NBKD_EINVAL, pairwise lines of sight are defined for non-periodic trees only
+ * (nbkd_query_ball_hist2 serves the periodic box).
+ * Out of scope: pair weights, per-query rows, jackknife regions, periodic
+ * trees, and other line-of-sight conventions (the bisector of the two
+ * directions, the first point's direction).
+ */
+nbkd_status nbkd_query_ball_hist2_obs(const nbkd_tree *tree, const float *q, uint64_t m,
+                                      int32_t mode,            /* NBKD_HIST2_RPPI | NBKD_HIST2_SMU */
+                                      const float *observer,   /* (3,) host memory, finite */
+                                      const float *edges1, int32_t n1,
+                                      const float *edges2, int32_t n2,
+                                      uint64_t *out_total,     /* (n1, n2) row-major, host */
+                                      uint32_t flags, void *stream);
+
+/*
  * NEW (no reference counterpart): friends-of-friends groups of the tree's own
  * points, the halo finder's first step.  Points i and j are friends iff
  * d2(i, j) <= b*b in float32, with d2 the tree's metric and b*b formed in

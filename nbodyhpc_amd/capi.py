@@ -56,6 +56,8 @@ _PROTOS = {
     "nbkd_query_ball_hist": (_i32, [_c_p, _c_p, _u64, _c_p, _i32, _c_p, _c_p, _u32, _c_p]),
     "nbkd_query_ball_hist2": (_i32, [_c_p, _c_p, _u64, _i32, _i32, _c_p, _i32, _c_p, _i32, _c_p,
                                      _u32, _c_p]),
+    "nbkd_query_ball_hist2_obs": (_i32, [_c_p, _c_p, _u64, _i32, _c_p, _c_p, _i32, _c_p, _i32,
+                                         _c_p, _u32, _c_p]),
     "nbkd_query_ball_sum": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _u32,
                                    _c_p]),
     "nbkd_query_ball_profile": (_i32, [_c_p, _c_p, _u64, _c_p, _c_p, _i32, _c_p, _i32, _c_p, _u32,
@@ -301,6 +303,34 @@ class Tree:
         _check(lib().nbkd_query_ball_hist2(self.h, q_ptr, int(m), int(mode), int(los),
                                            e1.ctypes.data, e1.shape[0], e2.ctypes.data,
                                            e2.shape[0], t.ctypes.data, NBKD_INPUT_DEVICE, stream))
+        return t
+
+    def ball_hist2_obs(self, q, edges1, edges2, mode, observer):
+        """nbkd_query_ball_hist2_obs of host queries: the (n1, n2) uint64 pair
+        counts with each pair's line of sight from ``observer`` (3 floats)
+        through the pair's midpoint."""
+        q = _host_f32(q).reshape(-1, 3)
+        e1 = _host_f32(edges1).reshape(-1)
+        e2 = _host_f32(edges2).reshape(-1)
+        o = _host_f32(observer).reshape(3)
+        t = np.empty((e1.shape[0], e2.shape[0]), np.uint64)
+        _check(lib().nbkd_query_ball_hist2_obs(self.h, q.ctypes.data, q.shape[0], int(mode),
+                                               o.ctypes.data, e1.ctypes.data, e1.shape[0],
+                                               e2.ctypes.data, e2.shape[0], t.ctypes.data, 0,
+                                               None))
+        return t
+
+    def ball_hist2_obs_device(self, q_ptr, m, edges1, edges2, mode, observer, stream=None):
+        """Device queries; returns the (n1, n2) uint64 pair counts (the call
+        waits for them)."""
+        e1 = _host_f32(edges1).reshape(-1)
+        e2 = _host_f32(edges2).reshape(-1)
+        o = _host_f32(observer).reshape(3)
+        t = np.empty((e1.shape[0], e2.shape[0]), np.uint64)
+        _check(lib().nbkd_query_ball_hist2_obs(self.h, q_ptr, int(m), int(mode), o.ctypes.data,
+                                               e1.ctypes.data, e1.shape[0], e2.ctypes.data,
+                                               e2.shape[0], t.ctypes.data, NBKD_INPUT_DEVICE,
+                                               stream))
         return t
 
     def ball_sum(self, q, h, values=None, kernel=1, count=False):

@@ -646,9 +646,10 @@ nbkd_status nbkd_query_ball_hist(const nbkd_tree *tree, const float *q, uint64_t
     NBKD_GUARD_END
 }
 
-// one axis of nbkd_query_ball_hist2's edges: false with the error set
-static bool hist2_edges_ok(const char *name, const float *e, int32_t n, int32_t nmax, bool mu) {
-    const std::string fn = "nbkd_query_ball_hist2: ";
+// one axis of nbkd_query_ball_hist2's (or _obs's) edges: false with the error set
+static bool hist2_edges_ok(const char *name, const float *e, int32_t n, int32_t nmax, bool mu,
+                           const char *func = "nbkd_query_ball_hist2") {
+    const std::string fn = std::string(func) + ": ";
     if (n < 1 || n > nmax) {
         set_error(fn + "the number of " + name + " edges must be in [1, " + std::to_string(nmax) +
                   "], got " + std::to_string(n));
@@ -705,6 +706,53 @@ nbkd_status nbkd_query_ball_hist2(const nbkd_tree *tree, const float *q, uint64_
     DeviceGuard g(tree->t.device);
     return query_ball_hist2(tree->t, q, m, mode, los, edges1, n1, edges2, n2, out_total, flags,
                             (hipStream_t)stream);
+    NBKD_GUARD_END
+}
+
+nbkd_status nbkd_query_ball_hist2_obs(const nbkd_tree *tree, const float *q, uint64_t m,
+                                      int32_t mode, const float *observer, const float *edges1,
+                                      int32_t n1, const float *edges2, int32_t n2,
+                                      uint64_t *out_total, uint32_t flags, void *stream) {
+    NBKD_GUARD_BEGIN
+    g_err.clear();
+    const char *const fn = "nbkd_query_ball_hist2_obs";
+    if (!tree || !q || !observer || !edges1 || !edges2 || !out_total) {
+        set_error("nbkd_query_ball_hist2_obs: NULL argument (tree, q, observer, edges1, edges2 "
+                  "or out_total)");
+        return NBKD_EINVAL;
+    }
+    if (mode != NBKD_HIST2_RPPI && mode != NBKD_HIST2_SMU) {
+        set_error("nbkd_query_ball_hist2_obs: unknown mode " + std::to_string(mode));
+        return NBKD_EINVAL;
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (!(observer[a] >= -FLT_MAX && observer[a] <= FLT_MAX)) {
+            set_error("nbkd_query_ball_hist2_obs: observer component " + std::to_string(a) +
+                      " is NaN or infinite");
+            return NBKD_EINVAL;
+        }
+    }
+    if (!hist2_edges_ok("first-axis", edges1, n1, NBKD_MAX_RADII, false, fn) ||
+        !hist2_edges_ok("second-axis", edges2, n2, NBKD_MAX_LOS_BINS, mode == NBKD_HIST2_SMU, fn))
+        return NBKD_EINVAL;
+    if (m >= (1ull << 32)) {
+        set_error("nbkd_query_ball_hist2_obs: more than 2^32 - 1 queries per call are not "
+                  "supported");
+        return NBKD_EINVAL;
+    }
+    if (m == 0) {
+        std::fill(out_total, out_total + (size_t)n1 * n2, (uint64_t)0);
+        return NBKD_OK;
+    }
+    if (tree->t.periodic) {
+        set_error("nbkd_query_ball_hist2_obs: the tree is periodic; pairwise lines of sight are "
+                  "defined for non-periodic trees only (nbkd_query_ball_hist2 takes the line of "
+                  "sight along an axis)");
+        return NBKD_EINVAL;
+    }
+    DeviceGuard g(tree->t.device);
+    return query_ball_hist2_obs(tree->t, q, m, mode, observer, edges1, n1, edges2, n2, out_total,
+                                flags, (hipStream_t)stream);
     NBKD_GUARD_END
 }
 

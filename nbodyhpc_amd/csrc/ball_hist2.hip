@@ -37,6 +37,17 @@
 // points) adds the leaf's count to that bin without evaluating a point.  The
 // others evaluate the staged points against the thresholds between the
 // wave-wide smallest lower and largest upper index only.
+//
+// Observer frame (nbkd_query_ball_hist2_obs, LOS == HIST2_LOS_OBS): the line of
+// sight of a pair runs from the observer o through the pair's midpoint.  With
+// s = p - q and l = fl(fl(p - o) + fl(q - o)) (twice the midpoint's offset),
+// pi2 = min(fl(fl(dot(s, l)^2) / l2), s2) and rp2 = fl(s2 - pi2): hist2_coords_obs,
+// the header's formulas operation by operation.  Non-periodic trees only.  The
+// per-axis cylinder bounds above do not hold for it; per leaf only
+// lb_s2 <= s2 <= ub_s2 and 0 <= rp2, pi2 <= s2 do (the clamp and s2 - pi2 with
+// 0 <= pi2 <= s2 keep both in float32), so a lane needs a leaf iff lb_s2 <= the
+// walk's bound, every lower index but SMU's first axis is 0 and every upper
+// bound is ub_s2.
 #include <algorithm>
 #include <cfloat>
 
@@ -111,6 +122,29 @@ __device__ __forceinline__ void hist2_coords(const float ax, const float ay, con
         x1 = (ax + ay) + az;
 }
 
+// the observer frame: the lane's query relative to the observer, fl(q - o),
+// formed once per lane, and the observer (wave-uniform)
+struct Hist2Obs {
+    float ox, oy, oz, qox, qoy, qoz;
+};
+
+// (x1, pi2) of one pair in the observer frame, the operations of include/nbkd.h
+// in their order (no contraction: -ffp-contract=off; x / l2 is the correctly
+// rounded division).  fminf takes s2 where the quotient is NaN (inf / inf).
+template <int MODE>
+__device__ __forceinline__ void hist2_coords_obs(const float qx, const float qy, const float qz,
+                                                 const float px, const float py, const float pz,
+                                                 const Hist2Obs &o, float &x1, float &pi2) {
+    const float sx = px - qx, sy = py - qy, sz = pz - qz;
+    const float s2 = (sx * sx + sy * sy) + sz * sz;
+    const float lx = (px - o.ox) + o.qox, ly = (py - o.oy) + o.qoy, lz = (pz - o.oz) + o.qoz;
+    const float dot = (sx * lx + sy * ly) + sz * lz;
+    const float l2 = (lx * lx + ly * ly) + lz * lz;
+    const float x = dot * dot;
+    pi2 = l2 > 0.0f ? fminf(x / l2, s2) : 0.0f;
+    x1 = MODE == NBKD_HIST2_RPPI ? s2 - pi2 : s2;
+}
+
 // the staged points against the thresholds [k0, k1) and [l0, l1) (every
 // evaluating lane fails the ones below and passes the ones above)
 template <bool M, int MODE, int LOS>
@@ -118,7 +152,7 @@ __device__ __forceinline__ void hist2_chunk(const float4 *p4s, const uint32_t cn
                                             const Hist2Ctx &c, const int k0, const int k1,
                                             const int l0, const int l1, const bool ev,
                                             const uint32_t copy, const float qx, const float qy,
-                                            const float qz, const float L) {
+                                            const float qz, const float L, const Hist2Obs &o) {
 #pragma unroll 1
     for (uint32_t u = 0; u < cn; u += EV) {
         float x1[EV], pi2[EV];
@@ -126,9 +160,13 @@ __device__ __forceinline__ void hist2_chunk(const float4 *p4s, const uint32_t cn
 #pragma unroll
         for (int i = 0; i < EV; ++i) {
             const float4 a = p4s[u + i];
-            float ax, ay, az;
-            point_axes_fast<M>(qx, qy, qz, a.x, a.y, a.z, L, ax, ay, az);
-            hist2_coords<MODE, LOS>(ax, ay, az, x1[i], pi2[i]);
+            if constexpr (LOS == HIST2_LOS_OBS) {
+                hist2_coords_obs<MODE>(qx, qy, qz, a.x, a.y, a.z, o, x1[i], pi2[i]);
+            } else {
+                float ax, ay, az;
+                point_axes_fast<M>(qx, qy, qz, a.x, a.y, a.z, L, ax, ay, az);
+                hist2_coords<MODE, LOS>(ax, ay, az, x1[i], pi2[i]);
+            }
             b1[i] = (uint32_t)k0;
             b2[i] = (uint32_t)l0;
         }
@@ -160,7 +198,9 @@ template <bool PER, bool M, int MODE, int LOS>
 __device__ __forceinline__ void hist2_walk(const DevTree &t, const uint32_t *__restrict__ linfo,
                                            float4 *p4s, const Hist2Ctx &c,
                                            const int lane, const float qx, const float qy,
-                                           const float qz, const float kth, const bool active) {
+                                           const float qz, const float kth, const bool active,
+                                           const Hist2Obs &o) {
+    static_assert(LOS != HIST2_LOS_OBS || (!PER && !M), "pairwise lines of sight: no periodic tree");
     const float L = t.box;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const cbox_ptr cboxes = (cbox_ptr)t.nbox;
@@ -180,9 +220,20 @@ __device__ __forceinline__ void hist2_walk(const DevTree &t, const uint32_t *__r
         const float ly = box_lb_axis<M>(qy, tb[2], tb[3], L);
         const float lz = box_lb_axis<M>(qz, tb[4], tb[5], L);
         float lb1, lbp;
-        hist2_coords<MODE, LOS>(lx, ly, lz, lb1, lbp);
-        bool need = active && lb1 <= t1max;
-        if constexpr (MODE == NBKD_HIST2_RPPI) need = need && lbp <= t2max;
+        bool need;
+        if constexpr (LOS == HIST2_LOS_OBS) {
+            // lb_s2 <= s2 for every point (box_lb2's association); rp2 and pi2
+            // reach down to 0 whatever the leaf.  kth is the walk's bound on s2
+            // for an active lane, -inf otherwise.
+            const float lbs = (lx + ly) + lz;
+            lb1 = MODE == NBKD_HIST2_SMU ? lbs : 0.0f;
+            lbp = 0.0f;
+            need = lbs <= kth;
+        } else {
+            hist2_coords<MODE, LOS>(lx, ly, lz, lb1, lbp);
+            need = active && lb1 <= t1max;
+            if constexpr (MODE == NBKD_HIST2_RPPI) need = need && lbp <= t2max;
+        }
         if (!__any(need)) continue;
         // (a leaf holding padding points, in no bin, is always evaluated, against
         // every threshold: the upper bounds do not hold for them)
@@ -192,7 +243,10 @@ __device__ __forceinline__ void hist2_walk(const DevTree &t, const uint32_t *__r
         const float hy = fmaxf(fabsf(tb[2] - qy), fabsf(tb[3] - qy));
         const float hz = fmaxf(fabsf(tb[4] - qz), fabsf(tb[5] - qz));
         float ub1, ubp;
-        hist2_coords<MODE, LOS>(hx * hx, hy * hy, hz * hz, ub1, ubp);
+        if constexpr (LOS == HIST2_LOS_OBS) // rp2 <= s2 and pi2 <= s2 <= ub_s2 (box_ub2)
+            ub1 = ubp = (hx * hx + hy * hy) + hz * hz;
+        else
+            hist2_coords<MODE, LOS>(hx * hx, hy * hy, hz * hz, ub1, ubp);
         // lo <= b <= hi for every point of the leaf, on both axes.  SMU: a
         // threshold l fails for every point when lbp > fl(T2[l] * ub1) (the
         // product is monotone in s2 <= ub1) and holds when ubp <= fl(T2[l] * lb1).
@@ -247,9 +301,10 @@ __device__ __forceinline__ void hist2_walk(const DevTree &t, const uint32_t *__r
             wait_vm0();
             wave_sync();
             if (plain_leaf)
-                hist2_chunk<false, MODE, LOS>(p4s, cn, c, k0, k1, l0, l1, ev, copy, qx, qy, qz, L);
+                hist2_chunk<false, MODE, LOS>(p4s, cn, c, k0, k1, l0, l1, ev, copy, qx, qy, qz, L,
+                                              o);
             else
-                hist2_chunk<M, MODE, LOS>(p4s, cn, c, k0, k1, l0, l1, ev, copy, qx, qy, qz, L);
+                hist2_chunk<M, MODE, LOS>(p4s, cn, c, k0, k1, l0, l1, ev, copy, qx, qy, qz, L, o);
         }
     }
 }
@@ -292,10 +347,12 @@ ball_hist2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__
     // point inside the ball, and a point outside it is in no bin either way)
     bool plain = false;
     if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
+    // (read by the observer-frame instances only)
+    const Hist2Obs o{P.obs[0], P.obs[1], P.obs[2], qx - P.obs[0], qy - P.obs[1], qz - P.obs[2]};
     if (plain)
-        hist2_walk<PER, false, MODE, LOS>(t, linfo, p4s, c, lane, qx, qy, qz, kth, active);
+        hist2_walk<PER, false, MODE, LOS>(t, linfo, p4s, c, lane, qx, qy, qz, kth, active, o);
     else
-        hist2_walk<PER, PER, MODE, LOS>(t, linfo, p4s, c, lane, qx, qy, qz, kth, active);
+        hist2_walk<PER, PER, MODE, LOS>(t, linfo, p4s, c, lane, qx, qy, qz, kth, active, o);
     hist2_flush(c, lane);
 }
 
@@ -355,6 +412,13 @@ hist2_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *_
 //     > (A + B)(1 + 5u) covers it.  Where the product underflows (A + B below
 //     2^-126) every sum involved is exact, s2 = S <= A + B = fl(A + B), and W >=
 //     fl(A + B) because a product by a factor >= 1 rounds monotonically.
+//   observer frame (los = HIST2_LOS_OBS): rp2 = fl(s2 - pi2) <= A and pi2 <= B.
+//     The difference rounds as (s2 - pi2)(1 + d), |d| <= u (exactly in the
+//     subnormal range: a float32 difference loses no bits to underflow), so
+//     s2 - pi2 <= A / (1 - u), s2 <= A / (1 - u) + B <= (A + B) / (1 - u) <
+//     (A + B)(1 + 2u), below the (A + B)(1 + 5u) that W exceeds; where the
+//     product underflows the difference is exact and s2 <= A + B = fl(A + B) <= W.
+//     SMU is the bin test itself there too.
 // An overflowing bound is infinite: every leaf is then walked, which is valid.
 static float hist2_walk_bound(const Hist2Thr &thr, const Hist2Par &par) {
     const float A = thr.t1[par.n1 - 1];
@@ -394,7 +458,12 @@ void launch_ball_hist2(const Tree &t, const float *q, const uint32_t *order, uin
         else                                                                                       \
             NBKD_H2_LAUNCH(PERV, MODEV, 2);                                                        \
     } while (0)
-    if (t.periodic) {
+    if (par.los == HIST2_LOS_OBS) { // (non-periodic trees only: checked by the C entry point)
+        if (smu)
+            NBKD_H2_LAUNCH(false, NBKD_HIST2_SMU, HIST2_LOS_OBS);
+        else
+            NBKD_H2_LAUNCH(false, NBKD_HIST2_RPPI, HIST2_LOS_OBS);
+    } else if (t.periodic) {
         if (smu)
             NBKD_H2_LOS(true, NBKD_HIST2_SMU);
         else

@@ -463,6 +463,9 @@ void launch_ball_hist_outside_dev(const Tree &t, const float *q, const uint32_t 
 // kernel and answered by the second launch (list length in device memory).
 constexpr uint32_t HIST2_LDS_WORDS = NBKD_MAX_RADII * NBKD_MAX_LOS_BINS; // 8 KiB per wave
 constexpr int HIST2_DEFAULT_COPIES = 2; // measured: DESIGN.md section 3
+// par.los of nbkd_query_ball_hist2_obs: the line of sight of each pair runs from
+// par.obs through the pair's midpoint (non-periodic trees only)
+constexpr int HIST2_LOS_OBS = 3;
 struct Hist2Thr {
     float t1[NBKD_MAX_RADII];
     float t2[NBKD_MAX_LOS_BINS];
@@ -471,6 +474,7 @@ struct Hist2Par {
     int n1, n2, mode, los, rshift;
     uint32_t flush_visits; // flush the wave's histogram every so many leaf visits (0: wrap bound)
     float bound;           // the walk's bound on d2
+    float obs[3];          // the observer (los == HIST2_LOS_OBS)
 };
 int hist2_copies_shift(int nbins, int copies);
 void launch_ball_hist2(const Tree &t, const float *q, const uint32_t *order, uint32_t m,
@@ -562,6 +566,12 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
 nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode, int los,
                              const float *edges1, int n1, const float *edges2, int n2,
                              uint64_t *out_total, uint32_t flags, hipStream_t s);
+// the same with each pair's line of sight from observer (3 finite floats, host)
+// through the pair's midpoint; t is not periodic (checked by the caller)
+nbkd_status query_ball_hist2_obs(const Tree &t, const float *q, uint64_t m, int mode,
+                                 const float *observer, const float *edges1, int n1,
+                                 const float *edges2, int n2, uint64_t *out_total, uint32_t flags,
+                                 hipStream_t s);
 
 // h, values: on q's side; nv, kernel and the NULL cases checked by the caller
 // (api.cpp); m > 0

@@ -6,7 +6,8 @@
 // k=1, workers=1)), same properties (n = padded count, size = node count,
 // periodic, boxsize) and the same RuntimeError messages.  Differences, all
 // additive: a trailing `device` constructor argument, radius queries
-// (query_ball_count / query_ball_csr / query_ball_hist / query_ball_hist2),
+// (query_ball_count / query_ball_csr / query_ball_hist / query_ball_hist2 /
+// query_ball_hist2_obs),
 // kernel-weighted sums (ball_sum), radial profiles (ball_profile), gravity,
 // gravity_ewald, fof_labels, group_moments, group_potential and export() for
 // parity tests.
@@ -224,6 +225,40 @@ class PyKDTree {
             py::gil_scoped_release nogil;
             st = nbkd_query_ball_hist2(h_, q, (uint64_t)m, (int32_t)mode, (int32_t)los, e1,
                                        (int32_t)n1, e2, (int32_t)n2, tp, 0u, nullptr);
+        }
+        intr.finish(st);
+        return total;
+    }
+
+    // the same in the observer frame (nbkd_query_ball_hist2_obs): each pair's
+    // line of sight from observer (3 floats) through the pair's midpoint
+    py::array_t<uint64_t> query_ball_hist2_obs(farray points, farray edges1, farray edges2,
+                                               int mode, farray observer) {
+        check_shape(points);
+        if (edges1.ndim() != 1 || edges2.ndim() != 1)
+            throw std::runtime_error("the edges must be 1D arrays");
+        if (observer.ndim() != 1 || observer.shape(0) != 3)
+            throw std::runtime_error("observer must be a 1D array of 3 coordinates");
+        const py::ssize_t m = points.shape(0), n1 = edges1.shape(0), n2 = edges2.shape(0);
+        if (n1 < 1 || n1 > NBKD_MAX_RADII)
+            throw std::runtime_error("the number of first-axis edges must be in [1, " +
+                                     std::to_string(NBKD_MAX_RADII) + "]");
+        if (n2 < 1 || n2 > NBKD_MAX_LOS_BINS)
+            throw std::runtime_error("the number of second-axis edges must be in [1, " +
+                                     std::to_string(NBKD_MAX_LOS_BINS) + "]");
+        py::array_t<uint64_t> total({n1, n2});
+        const float *q = points.data(), *e1 = edges1.data(), *e2 = edges2.data();
+        const float *o = observer.data();
+        uint64_t *tp = total.mutable_data();
+        // (m == 0: no array to point at; the library only zeroes the totals)
+        const float dummy[3] = {0.0f, 0.0f, 0.0f};
+        if (m == 0) q = dummy;
+        nbkd_status st;
+        Interruptible intr;
+        {
+            py::gil_scoped_release nogil;
+            st = nbkd_query_ball_hist2_obs(h_, q, (uint64_t)m, (int32_t)mode, o, e1, (int32_t)n1,
+                                           e2, (int32_t)n2, tp, 0u, nullptr);
         }
         intr.finish(st);
         return total;
@@ -552,6 +587,8 @@ PYBIND11_MODULE(_impl, m) {
              py::arg("per_point") = false)
         .def("query_ball_hist2", &PyKDTree::query_ball_hist2, py::arg("points"),
              py::arg("edges1"), py::arg("edges2"), py::arg("mode"), py::arg("los") = 2)
+        .def("query_ball_hist2_obs", &PyKDTree::query_ball_hist2_obs, py::arg("points"),
+             py::arg("edges1"), py::arg("edges2"), py::arg("mode"), py::arg("observer"))
         .def("query_ball_csr", &PyKDTree::query_ball_csr, py::arg("points"), py::arg("r"),
              py::arg("sorted") = true)
         .def("ball_sum", &PyKDTree::ball_sum, py::arg("points"), py::arg("h"),

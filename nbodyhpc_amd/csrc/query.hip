@@ -2220,16 +2220,19 @@ static nbkd_status hist2_common(const Tree &t, Workspace &ws, const float *q, ui
         NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
         outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
     }
-    TimedScope ts("ball_hist2", s);
+    TimedScope ts(par.los == HIST2_LOS_OBS ? "ball_hist2_obs" : "ball_hist2", s);
     launch_ball_hist2(t, dq, ord, mm, thr, par, tot, s);
     if (list) launch_ball_hist2_outside_dev(t, dq, list, list + mm, thr, par, tot, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
 
-nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode, int los,
-                             const float *edges1, int n1, const float *edges2, int n2,
-                             uint64_t *out_total, uint32_t flags, hipStream_t s) {
+// nbkd_query_ball_hist2 (observer == nullptr, los an axis) and
+// nbkd_query_ball_hist2_obs (los == HIST2_LOS_OBS): one host pipeline
+static nbkd_status hist2_call(const Tree &t, const float *q, uint64_t m, int mode, int los,
+                              const float *observer, const float *edges1, int n1,
+                              const float *edges2, int n2, uint64_t *out_total, uint32_t flags,
+                              hipStream_t s) {
     const size_t nbins = (size_t)n1 * n2;
     std::fill(out_total, out_total + nbins, (uint64_t)0);
     if (m == 0 || t.n == 0 || t.nnodes == 0) return NBKD_OK;
@@ -2253,6 +2256,7 @@ nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode
     par.rshift = hist2_copies_shift((int)nbins, (int)std::min(tuning(TUNE_HIST2_COPIES), 64.0));
     par.flush_visits = (uint32_t)std::min(tuning(TUNE_HIST2_FLUSH), 4294967295.0);
     par.bound = 0.0f;
+    for (int a = 0; a < 3; ++a) par.obs[a] = observer ? observer[a] : 0.0f;
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
@@ -2277,6 +2281,20 @@ nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode
     NBKD_HIP(hipMemcpyAsync(out_total, tot, nbins * 8, hipMemcpyDeviceToHost, s));
     NBKD_HIP(hipStreamSynchronize(s));
     return NBKD_OK;
+}
+
+nbkd_status query_ball_hist2(const Tree &t, const float *q, uint64_t m, int mode, int los,
+                             const float *edges1, int n1, const float *edges2, int n2,
+                             uint64_t *out_total, uint32_t flags, hipStream_t s) {
+    return hist2_call(t, q, m, mode, los, nullptr, edges1, n1, edges2, n2, out_total, flags, s);
+}
+
+nbkd_status query_ball_hist2_obs(const Tree &t, const float *q, uint64_t m, int mode,
+                                 const float *observer, const float *edges1, int n1,
+                                 const float *edges2, int n2, uint64_t *out_total, uint32_t flags,
+                                 hipStream_t s) {
+    return hist2_call(t, q, m, mode, HIST2_LOS_OBS, observer, edges1, n1, edges2, n2, out_total,
+                      flags, s);
 }
 
 namespace {

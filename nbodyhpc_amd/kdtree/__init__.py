@@ -12,7 +12,10 @@ query, count or index lists), ``count_neighbors`` / ``pair_counts`` (counts at
 many radii in one tree walk), ``count_pairs_rppi`` / ``count_pairs_smu`` /
 ``pair_counts_rppi`` / ``pair_counts_smu`` / ``xi_rppi`` / ``xi_smu``
 (anisotropic pair counts about a line of sight in one tree walk, wp(rp) and
-the multipoles from them), ``fof`` / ``fof_labels`` (friends-of-friends
+the multipoles from them; with ``observer=`` the line of sight of each pair
+runs from the observer through the pair's midpoint, for light cones and survey
+mocks), ``landy_szalay`` / ``xi_rppi_ls`` / ``xi_smu_ls`` (the same from DD, DR
+and RR against a random catalogue), ``fof`` / ``fof_labels`` (friends-of-friends
 groups of the tree's points), ``fof_catalog`` (members, mass, centre, extent
 and value moments per group, reduced on the GPU), ``density`` (local number density from the k-th
 neighbour distance or from a radius count), ``kernel_sum`` / ``sph_density`` /
@@ -49,7 +52,7 @@ except ImportError as e:  # fail loudly: no CPU path exists
         "nbodyhpc_amd.kdtree._impl is not built; run `python -m nbodyhpc_amd.build` "
         f"(hipcc for gfx950 + pybind11). Original error: {e}") from e
 
-__all__ = ["KDTree", "cKDTree", "device_count"]
+__all__ = ["KDTree", "cKDTree", "device_count", "landy_szalay"]
 
 # kernel name -> (NBKD_KERNEL_* code, 3-D normalisation sigma of K(d / h) / h^3
 # with support radius h)
@@ -69,12 +72,51 @@ def _flatten(points):
     return points, None
 
 
+def _obs_kw(observer):
+    """the ``observer`` keyword of the count methods, left out when None"""
+    return {} if observer is None else {"observer": observer}
+
+
+def _multipoles(xi, u, ells):
+    """{ell: (2 ell + 1) sum_l xi P_ell(mu_mid) dmu} of xi (ns, nmu) on the mu
+    edges u (nmu + 1,), float64"""
+    dmu = u[1:] - u[:-1]
+    mid = 0.5 * (u[1:] + u[:-1])
+    poles = {}
+    for ell in ells:
+        c = np.zeros(int(ell) + 1)
+        c[int(ell)] = 1.0
+        leg = np.polynomial.legendre.legval(mid, c)
+        poles[int(ell)] = (2 * int(ell) + 1) * (xi * (leg * dmu)[None, :]).sum(axis=1)
+    return poles
+
+
 def _geometric(lo, hi, n):
     """n float32 edges from lo to hi in equal ratios, ascending (the two ends
     exact: the float32 values of lo and hi)"""
     g = np.exp(np.linspace(math.log(lo), math.log(hi), n)).astype(np.float32)
     g[0], g[-1] = np.float32(lo), np.float32(hi)
     return np.maximum.accumulate(g)
+
+
+def landy_szalay(dd, dr, rr, nd, nr):
+    """The Landy-Szalay estimator per bin, in float64:
+    ``(DD / (nd (nd - 1)) - 2 DR / (nd nr) + RR / (nr (nr - 1))) / (RR / (nr (nr - 1)))``,
+    NaN where ``rr == 0``.
+
+    dd, rr : ordered pair counts of the nd data points and of the nr random
+        points among themselves, self pairs removed (both orders of a pair
+        counted, as ``count_pairs_rppi`` / ``count_pairs_smu`` count them).
+    dr : the counts of the data as queries against the randoms' tree.
+    """
+    dd = np.asarray(dd, dtype=np.float64)
+    dr = np.asarray(dr, dtype=np.float64)
+    rr = np.asarray(rr, dtype=np.float64)
+    nd, nr = float(nd), float(nr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rrn = rr / (nr * (nr - 1.0))
+        xi = (dd / (nd * (nd - 1.0)) - 2.0 * dr / (nd * nr) + rrn) / rrn
+    return np.where(rr == 0, np.nan, xi)
 
 
 class KDTree(cKDTree):
@@ -220,15 +262,36 @@ class KDTree(cKDTree):
             raise ValueError(f"{name} must be ascending (non-decreasing)")
         return np.ascontiguousarray(e)
 
-    def _count_pairs2(self, points, e1, e2, mode, los, names):
+    def _observer(self, observer, los):
+        """the float32 observer of the pairwise line of sight, checked"""
+        if los != 2:
+            raise ValueError("give los or observer, not both")
+        if self.periodic:
+            raise ValueError("observer needs a non-periodic tree: pairwise lines of sight are "
+                             "not defined on a periodic one (los takes an axis there)")
+        try:
+            o = np.asarray(observer, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("observer must be 3 finite coordinates") from None
+        with np.errstate(over="ignore"):
+            o32 = o.astype(np.float32)
+        if o.shape != (3,) or not np.all(np.isfinite(o32)):
+            raise ValueError(f"observer must be 3 finite coordinates, got {observer!r}")
+        return np.ascontiguousarray(o32)
+
+    def _count_pairs2(self, points, e1, e2, mode, los, names, observer=None):
         e1 = self._edges(e1, names[0], _MAX_RADII)
         e2 = self._edges(e2, names[1], _MAX_LOS_BINS, mu=mode == _HIST2_SMU)
         if los not in (0, 1, 2):
             raise ValueError("los must be 0, 1 or 2 (the axis of the line of sight)")
+        if observer is not None:
+            o = self._observer(observer, los)
+            points, _ = _flatten(points)
+            return super().query_ball_hist2_obs(points, e1, e2, mode, o)
         points, _ = _flatten(points)
         return super().query_ball_hist2(points, e1, e2, mode, int(los))
 
-    def count_pairs_rppi(self, points: np.ndarray, rp, pi, los: int = 2):
+    def count_pairs_rppi(self, points: np.ndarray, rp, pi, los: int = 2, observer=None):
         """Pair counts of ``points`` against the tree's points in (rp, pi) bins,
         one tree walk: uint64 (len(rp), len(pi)).  rp (up to 32) and pi (up to
         64) are ascending edges, each finite and >= 0; ``los`` is the axis of the
@@ -237,17 +300,26 @@ class KDTree(cKDTree):
         other two, a pair falls into bin (#{k: rp2 > rp[k]^2}, #{l: pi2 >
         pi[l]^2}) and is dropped when either index runs past the last edge: bins
         are differential on both axes, bin 0 reaches from 0 to the first edge.
-        Cross counts D1D2, DR and RR come from passing the other catalogue."""
-        return self._count_pairs2(points, rp, pi, _HIST2_RPPI, los, ("rp", "pi"))
+        Cross counts D1D2, DR and RR come from passing the other catalogue.
 
-    def count_pairs_smu(self, points: np.ndarray, s, mu, los: int = 2):
+        observer : None, or 3 finite coordinates (non-periodic trees only, and
+            instead of ``los``): the line of sight of each pair then runs from
+            the observer through the pair's midpoint.  With s = p - q and l =
+            (p - o) + (q - o), pi2 = min((s . l)^2 / |l|^2, s2) (0 where l = 0)
+            and rp2 = s2 - pi2, all in float32 (include/nbkd.h,
+            nbkd_query_ball_hist2_obs)."""
+        return self._count_pairs2(points, rp, pi, _HIST2_RPPI, los, ("rp", "pi"), observer)
+
+    def count_pairs_smu(self, points: np.ndarray, s, mu, los: int = 2, observer=None):
         """Pair counts of ``points`` against the tree's points in (s, mu) bins,
         one tree walk: uint64 (len(s), len(mu)).  s (up to 32 edges) bins the
         tree's own distance (s2 = d2 of ``count_neighbors``), mu (up to 64 edges
         in [0, 1]) bins |pi| / s through pi2 <= fl(mu[l]^2 * s2).  With a last mu
         edge of 1 every pair within s[-1] is counted, and the sum over mu equals
-        ``count_neighbors(points, s, cumulative=False)``."""
-        return self._count_pairs2(points, s, mu, _HIST2_SMU, los, ("s", "mu"))
+        ``count_neighbors(points, s, cumulative=False)``.  ``observer`` as in
+        ``count_pairs_rppi``: pi2 is then taken along the line from the observer
+        through the pair's midpoint."""
+        return self._count_pairs2(points, s, mu, _HIST2_SMU, los, ("s", "mu"), observer)
 
     def _auto2(self, counts):
         """ordered counts of the tree's own points -> unordered pairs: the n
@@ -256,19 +328,22 @@ class KDTree(cKDTree):
         counts[0, 0] -= np.uint64(self._n_input)
         return counts // np.uint64(2)
 
-    def pair_counts_rppi(self, rp, pi, los: int = 2):
+    def pair_counts_rppi(self, rp, pi, los: int = 2, observer=None):
         """Auto pair counts DD(rp, pi) of the tree's own points: unordered pairs
         i < j per bin (``count_pairs_rppi``'s bins), self pairs removed."""
-        return self._auto2(self.count_pairs_rppi(self.points(), rp, pi, los))
+        return self._auto2(self.count_pairs_rppi(self.points(), rp, pi, los, **_obs_kw(observer)))
 
-    def pair_counts_smu(self, s, mu, los: int = 2):
+    def pair_counts_smu(self, s, mu, los: int = 2, observer=None):
         """Auto pair counts DD(s, mu) of the tree's own points: unordered pairs
         i < j per bin (``count_pairs_smu``'s bins), self pairs removed."""
-        return self._auto2(self.count_pairs_smu(self.points(), s, mu, los))
+        return self._auto2(self.count_pairs_smu(self.points(), s, mu, los, **_obs_kw(observer)))
 
     def _xi_args(self, edges, name, nsec, nsec_name):
         if not self.periodic:
             raise ValueError("the natural estimator with analytic RR needs a periodic tree")
+        return self._xi_edges(edges, name, nsec, nsec_name)
+
+    def _xi_edges(self, edges, name, nsec, nsec_name):
         e = self._edges(edges, name, _MAX_RADII)
         if e.size < 2:
             raise ValueError(f"{name} needs at least two edges (one bin)")
@@ -327,14 +402,75 @@ class KDTree(cKDTree):
         dmu = u[1:] - u[:-1]
         vol = (4.0 * math.pi / 3.0) * (r[1:] ** 3 - r[:-1] ** 3)[:, None] * dmu[None, :]
         xi = dd / (n * (n / L ** 3) * vol) - 1.0
-        mid = 0.5 * (u[1:] + u[:-1])
-        poles = {}
-        for ell in ells:
-            c = np.zeros(int(ell) + 1)
-            c[int(ell)] = 1.0
-            leg = np.polynomial.legendre.legval(mid, c)
-            poles[int(ell)] = (2 * int(ell) + 1) * (xi * (leg * dmu)[None, :]).sum(axis=1)
-        return xi, poles
+        return xi, _multipoles(xi, u, ells)
+
+    def _ls_randoms(self, randoms):
+        if not isinstance(randoms, KDTree):
+            raise ValueError("randoms must be a KDTree of the random catalogue")
+        if bool(randoms.periodic) != bool(self.periodic) or (
+                self.periodic and float(randoms.boxsize) != float(self.boxsize)):
+            raise ValueError("randoms must have the tree's periodicity and box size")
+
+    def _ls_counts(self, randoms, count, e1, e2, los, observer):
+        """(DD, DR, RR) of ``count`` ("count_pairs_rppi" / "count_pairs_smu"),
+        ordered, without the first row (what lies inside the first edge, the
+        self pairs among it)"""
+        kw = _obs_kw(observer)
+        data = self.points()
+        dd = getattr(self, count)(data, e1, e2, los, **kw)[1:]
+        dr = getattr(randoms, count)(data, e1, e2, los, **kw)[1:]
+        rr = getattr(randoms, count)(randoms.points(), e1, e2, los, **kw)[1:]
+        return dd, dr, rr
+
+    def xi_rppi_ls(self, randoms, rp_edges, pi_max: float, npi: int, los: int = 2,
+                   observer=None):
+        """xi(rp, pi) and wp(rp) of the tree's points by the Landy-Szalay
+        estimator against a random catalogue, in float64: ``landy_szalay`` of
+        DD, DR and RR, three tree walks.
+
+        randoms : the KDTree of the random catalogue (same periodicity and box).
+        rp_edges, pi_max, npi : the bins of ``xi_rppi`` (what lies inside the
+            first rp edge is dropped; pi edges pi_max (l + 1) / npi rounded to
+            float32; on a periodic tree neither may pass half the box).
+        los, observer : as in ``count_pairs_rppi``; with an observer (a
+            non-periodic tree) each pair's line of sight runs through its
+            midpoint, the geometry of a light cone or a survey mock.
+        Returns (xi (n - 1, npi), wp (n - 1,)), wp = 2 sum_l xi dpi; NaN where
+        RR is 0."""
+        self._ls_randoms(randoms)
+        e, npi = self._xi_edges(rp_edges, "rp_edges", npi, "npi")
+        if not (math.isfinite(pi_max) and pi_max > 0):
+            raise ValueError("pi_max must be finite and > 0")
+        if self.periodic and (float(e[-1]) > 0.5 * float(self.boxsize)
+                              or pi_max > 0.5 * float(self.boxsize)):
+            raise ValueError("rp_edges[-1] and pi_max must not exceed half the box")
+        pe = (float(pi_max) * (np.arange(npi, dtype=np.float64) + 1.0) / npi).astype(np.float32)
+        dd, dr, rr = self._ls_counts(randoms, "count_pairs_rppi", e, pe, los, observer)
+        xi = landy_szalay(dd, dr, rr, self._n_input, randoms._n_input)
+        p = np.concatenate([[0.0], pe.astype(np.float64)])
+        wp = 2.0 * (xi * (p[1:] - p[:-1])[None, :]).sum(axis=1)
+        return xi, wp
+
+    def xi_smu_ls(self, randoms, s_edges, nmu: int, ells=(0, 2, 4), los: int = 2,
+                  observer=None):
+        """xi(s, mu) and its multipoles of the tree's points by the
+        Landy-Szalay estimator against a random catalogue, in float64.
+
+        randoms, los, observer : as in ``xi_rppi_ls``.
+        s_edges, nmu, ells : the bins and multipoles of ``xi_smu`` (mu edges
+            (l + 1) / nmu rounded to float32; xi_ell(s) = (2 ell + 1) sum_l xi
+            P_ell(mu_mid) dmu).
+        Returns (xi (n - 1, nmu), multipoles {ell: (n - 1,)}); NaN where RR is
+        0."""
+        self._ls_randoms(randoms)
+        e, nmu = self._xi_edges(s_edges, "s_edges", nmu, "nmu")
+        if self.periodic and float(e[-1]) > 0.5 * float(self.boxsize):
+            raise ValueError("s_edges[-1] must not exceed half the box")
+        me = ((np.arange(nmu, dtype=np.float64) + 1.0) / nmu).astype(np.float32)
+        dd, dr, rr = self._ls_counts(randoms, "count_pairs_smu", e, me, los, observer)
+        xi = landy_szalay(dd, dr, rr, self._n_input, randoms._n_input)
+        u = np.concatenate([[0.0], me.astype(np.float64)])
+        return xi, _multipoles(xi, u, ells)
 
     def fof(self, linking_length: float, min_members: int = 1, return_sizes: bool = False):
         """Friends-of-friends groups of the tree's own points: two points are
