@@ -32,8 +32,8 @@ ARCH = os.environ.get("NBKD_ARCH", "gfx950")
 # squared distances stop being bit-identical.
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
              "-Wall", "-Wno-unused-function", "-Wno-unused-const-variable"]
-SOURCES = ["api.cpp", "build.hip", "query.hip", "knn_collect.hip", "ball.hip", "ball_hist.hip",
-           "ball_hist2.hip", "ball_sum.hip", "ball_profile.hip", "gravity.hip",
+SOURCES = ["api.cpp", "build.hip", "query.hip", "sort.hip", "knn_collect.hip", "ball.hip",
+           "ball_hist.hip", "ball_hist2.hip", "ball_sum.hip", "ball_profile.hip", "gravity.hip",
            "gravity_ewald.hip", "fof.hip", "group.hip", "group_potential.hip", "slab.hip",
            "deposit.hip"]
 HEADERS = [os.path.join(CSRC, "internal.hpp"), os.path.join(CSRC, "metric.hpp"),

@@ -11,7 +11,7 @@
 //   scan x 2  pos[i] = kept rows before i, gidx[i] = kept heads before i
 //   compact   keys[pos[i]] = gidx[label[i]], members[pos[i]] = i: ascending
 //             rows; head[g], size[g]
-//   sort      sort_pairs (stable LSD radix) on the low ceil(log2 G) key bits:
+//   sort      radix_sort (stable LSD radix) on the low ceil(log2 G) key bits:
 //             groups ascending by head, rows ascending inside each: out_members
 //   offsets   off[g] = the first sorted position with key g
 //   inv       row -> tree position (one scatter of the build permutation)
@@ -464,16 +464,16 @@ nbkd_status group_catalog(const Tree &t, const uint32_t *label, const float *wei
     uint32_t *keys = k0, *members = v0;
     {
         TimedScope ts("group_sort", s);
-        nbkd_status rc = excl_scan(ws, pos, n, s);
+        nbkd_status rc = device_excl_scan(ws, pos, n, s);
         if (rc) return rc;
-        rc = excl_scan(ws, gidx, n, s);
+        rc = device_excl_scan(ws, gidx, n, s);
         if (rc) return rc;
         group_compact_kernel<<<blocks_for(n), TB, 0, s>>>(dlabel, n, cnt, mm, pos, gidx, k0, v0,
                                                          head, size);
         NBKD_HIP(hipGetLastError());
         if (G > 1) { // (one group: the compaction's row order is the result)
             const int nbits = 32 - __builtin_clz(G - 1);
-            rc = sort_pairs(ws, k0, v0, k1, v1, K, nbits, s, &members);
+            rc = radix_sort(ws, k0, v0, k1, v1, K, nbits, s, &members);
             if (rc) return rc;
             keys = members == v0 ? k0 : k1;
         }

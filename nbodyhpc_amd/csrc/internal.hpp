@@ -600,13 +600,13 @@ nbkd_status query_gravity_ewald(const Tree &t, const float *q, uint64_t m, const
 nbkd_status fof(const Tree &t, float b, uint32_t *out_label, uint32_t *out_size,
                 uint64_t *out_ngroups, uint32_t flags, hipStream_t s);
 
-// query.hip: LSD radix sort of (key, value) pairs by the low nbits of the keys,
+// sort.hip: LSD radix sort of (key, value) pairs by the low nbits of the keys,
 // ping-ponging (k0, v0) <-> (k1, v1); *vout = the buffer holding the sorted values
-nbkd_status sort_pairs(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
+nbkd_status radix_sort(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
                        uint32_t n, int nbits, hipStream_t s, uint32_t **vout);
 
-// query.hip: exclusive scan of a uint32 array in place (3 launches)
-nbkd_status excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s);
+// sort.hip: exclusive scan of a uint32 array in place (3 launches)
+nbkd_status device_excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s);
 
 // group.hip: the kept groups of a canonical labelling, their member lists and
 // float64 moments (the NULL cases, nv and the counts' pointers checked by the

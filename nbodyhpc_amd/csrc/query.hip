@@ -400,354 +400,6 @@ leaf_key2_kernel(const float *__restrict__ splits, const uint32_t *__restrict__ 
     }
 }
 
-// ------------------------------------------------------------------ LSD radix sort (keys + values)
-constexpr int RS_ITEMS = 8;
-constexpr int RS_TILE = TB * RS_ITEMS; // 2048
-
-__global__ void __launch_bounds__(TB)
-rs_hist_kernel(const uint32_t *__restrict__ keys, uint32_t n, int shift, uint32_t ntiles,
-               uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * RS_TILE;
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        uint32_t e = base + r * TB + threadIdx.x;
-        if (e < n) atomicAdd(&h[(keys[e] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(TB)
-rs_scatter_kernel(const uint32_t *__restrict__ kin, const uint32_t *__restrict__ vin, uint32_t n,
-                  int shift, uint32_t ntiles, const uint32_t *__restrict__ hist_scanned,
-                  uint32_t *__restrict__ kout, uint32_t *__restrict__ vout) {
-    __shared__ uint16_t cnt[RS_ITEMS][WPB][256];
-    __shared__ uint32_t gofs[256];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j = threadIdx.x; j < RS_ITEMS * WPB * 256; j += TB) (&cnt[0][0][0])[j] = 0;
-    gofs[threadIdx.x] = hist_scanned[(size_t)threadIdx.x * ntiles + blockIdx.x];
-    __syncthreads();
-    const uint32_t base = blockIdx.x * RS_TILE;
-    uint32_t kk[RS_ITEMS], vv[RS_ITEMS], rk[RS_ITEMS];
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        uint32_t e = base + r * TB + threadIdx.x;
-        bool valid = e < n;
-        kk[r] = valid ? kin[e] : 0u;
-        vv[r] = valid ? vin[e] : 0u;
-        uint32_t d = (kk[r] >> shift) & 255u;
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            uint64_t bb = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? bb : ~bb;
-        }
-        uint32_t below = mbcnt64(same);
-        rk[r] = below;
-        if (valid && below == 0) cnt[r][wave][d] = (uint16_t)__popcll(same);
-    }
-    __syncthreads();
-    { // per digit: exclusive prefix over (round, wave) in element order
-        uint32_t acc = 0;
-        const int d = threadIdx.x;
-        for (int r = 0; r < RS_ITEMS; ++r)
-            for (int w = 0; w < WPB; ++w) {
-                uint32_t v = cnt[r][w][d];
-                cnt[r][w][d] = (uint16_t)acc;
-                acc += v;
-            }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ITEMS; ++r) {
-        uint32_t e = base + r * TB + threadIdx.x;
-        if (e < n) {
-            uint32_t d = (kk[r] >> shift) & 255u;
-            uint32_t dst = gofs[d] + cnt[r][wave][d] + rk[r];
-            kout[dst] = kk[r];
-            vout[dst] = vv[r];
-        }
-    }
-    (void)lane;
-}
-
-// exclusive scan of a uint32 array, 3 kernels
-constexpr int SC_ITEMS = 16;
-constexpr int SC_TILE = TB * SC_ITEMS;
-
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t *sh, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nw = blockDim.x / 64;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (int w = 0; w < nw; ++w) {
-        uint32_t s = sh[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    if (total) *total = tot;
-    __syncthreads();
-    return base + x - v;
-}
-
-__global__ void __launch_bounds__(TB)
-scan_up_kernel(const uint32_t *__restrict__ a, uint64_t n, uint32_t *__restrict__ sums) {
-    __shared__ uint32_t sh[WPB];
-    const uint64_t base = (uint64_t)blockIdx.x * SC_TILE + (uint64_t)threadIdx.x * SC_ITEMS;
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < SC_ITEMS; ++j)
-        if (base + j < n) s += a[base + j];
-    uint32_t tot;
-    block_scan_excl(s, sh, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(1024) scan_mid_kernel(uint32_t *__restrict__ sums, uint32_t nb) {
-    __shared__ uint32_t sh[16];
-    const uint32_t per = (nb + 1023) / 1024;
-    const uint32_t b0 = threadIdx.x * per, b1 = min(b0 + per, nb);
-    uint32_t s = 0;
-    for (uint32_t b = b0; b < b1; ++b) s += sums[b];
-    uint32_t ex = block_scan_excl(s, sh, nullptr);
-    for (uint32_t b = b0; b < b1; ++b) {
-        uint32_t v = sums[b];
-        sums[b] = ex;
-        ex += v;
-    }
-}
-
-__global__ void __launch_bounds__(TB)
-scan_down_kernel(uint32_t *__restrict__ a, uint64_t n, const uint32_t *__restrict__ sums) {
-    __shared__ uint32_t sh[WPB];
-    const uint64_t base = (uint64_t)blockIdx.x * SC_TILE + (uint64_t)threadIdx.x * SC_ITEMS;
-    uint32_t v[SC_ITEMS], s = 0;
-#pragma unroll
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        v[j] = base + j < n ? a[base + j] : 0u;
-        s += v[j];
-    }
-    uint32_t ex = block_scan_excl(s, sh, nullptr) + sums[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < SC_ITEMS; ++j) {
-        if (base + j < n) a[base + j] = ex;
-        ex += v[j];
-    }
-}
-
-nbkd_status device_excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s) {
-    if (n == 0) return NBKD_OK;
-    uint64_t nb = (n + SC_TILE - 1) / SC_TILE;
-    uint32_t *sums = (uint32_t *)ws.get(WS_SUMS, nb * 4, s);
-    if (!sums) return NBKD_ENOMEM;
-    scan_up_kernel<<<(unsigned)nb, TB, 0, s>>>(a, n, sums);
-    scan_mid_kernel<<<1, 1024, 0, s>>>(sums, (uint32_t)nb);
-    scan_down_kernel<<<(unsigned)nb, TB, 0, s>>>(a, n, sums);
-    NBKD_HIP(hipGetLastError());
-    return NBKD_OK;
-}
-
-// ------------------------------------------------------------------ one-sweep LSD radix sort
-// One histogram read of the keys for all passes, then per 8-bit pass ONE kernel:
-// each 4096-item tile ranks its items (stable), publishes its digit counts,
-// finds its global digit offsets by decoupled look-back over the tiles before
-// it (tiles are numbered in start order by an atomic ticket, so every tile it
-// waits on is running), stages the tile digit-sorted in LDS and writes it out
-// in digit runs.  Per pass: 8 B read + 8 B written per item.
-constexpr int OS_ITEMS = 16;
-constexpr int OS_TILE = TB * OS_ITEMS; // 4096
-constexpr uint32_t OS_AGG = 1u << 30, OS_PRE = 2u << 30, OS_VAL = OS_AGG - 1;
-constexpr int OS_MAXP = 4;
-
-__global__ void __launch_bounds__(TB)
-os_hist_kernel(const uint32_t *__restrict__ keys, uint32_t n, int passes,
-               uint32_t *__restrict__ ghist) {
-    __shared__ uint32_t h[OS_MAXP][256];
-    for (int j = threadIdx.x; j < OS_MAXP * 256; j += TB) (&h[0][0])[j] = 0;
-    __syncthreads();
-    for (uint32_t i = blockIdx.x * TB + threadIdx.x; i < n; i += gridDim.x * TB) {
-        const uint32_t k = keys[i];
-        for (int p = 0; p < passes; ++p) atomicAdd(&h[p][(k >> (8 * p)) & 255u], 1u);
-    }
-    __syncthreads();
-    for (int p = 0; p < passes; ++p) {
-        const uint32_t v = h[p][threadIdx.x];
-        if (v) atomicAdd(&ghist[p * 256 + threadIdx.x], v);
-    }
-}
-
-// exclusive scan of each pass's 256 counts, in place (one block)
-__global__ void __launch_bounds__(TB) os_scan_kernel(uint32_t *__restrict__ ghist, int passes) {
-    __shared__ uint32_t sh[WPB];
-    for (int p = 0; p < passes; ++p) {
-        const uint32_t v = ghist[p * 256 + threadIdx.x];
-        ghist[p * 256 + threadIdx.x] = block_scan_excl(v, sh, nullptr);
-    }
-}
-
-__global__ void __launch_bounds__(TB)
-os_pass_kernel(const uint32_t *__restrict__ kin, const uint32_t *__restrict__ vin, uint32_t n,
-               int shift, const uint32_t *__restrict__ gexcl, uint32_t *__restrict__ status,
-               uint32_t *__restrict__ ticket, uint32_t *__restrict__ kout,
-               uint32_t *__restrict__ vout) {
-    __shared__ uint32_t wh[WPB][256]; // per wave digit counts, then wave-exclusive offsets
-    __shared__ uint32_t ls[256];      // tile-local digit start
-    __shared__ uint32_t gofs[256];    // global position of local index 0 of digit d
-    __shared__ uint32_t sk[OS_TILE], sv[OS_TILE];
-    __shared__ uint32_t sh[WPB];
-    __shared__ uint32_t tile_sh;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) tile_sh = atomicAdd(ticket, 1u);
-    for (int j = tid; j < WPB * 256; j += TB) (&wh[0][0])[j] = 0;
-    __syncthreads();
-    const uint32_t tile = tile_sh;
-    const uint32_t t0 = tile * (uint32_t)OS_TILE;
-    const uint32_t base = t0 + (uint32_t)wave * (OS_ITEMS * 64);
-    uint32_t kk[OS_ITEMS], vv[OS_ITEMS], rk[OS_ITEMS];
-#pragma unroll
-    for (int r = 0; r < OS_ITEMS; ++r) {
-        const uint32_t e = base + r * 64 + lane;
-        kk[r] = e < n ? kin[e] : 0xFFFFFFFFu;
-        vv[r] = e < n ? vin[e] : 0u;
-    }
-    // stable rank: items of wave w in element order, round by round
-#pragma unroll
-    for (int r = 0; r < OS_ITEMS; ++r) {
-        const uint32_t e = base + r * 64 + lane;
-        const uint32_t d = (kk[r] >> shift) & 255u;
-        uint64_t same = __ballot(e < n);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const uint64_t bb = __ballot((d >> b) & 1u);
-            same &= ((d >> b) & 1u) ? bb : ~bb;
-        }
-        const uint32_t below = mbcnt64(same);
-        const uint32_t old = wh[wave][d];
-        rk[r] = old + below;
-        if (e < n && below == 0) wh[wave][d] = old + (uint32_t)__popcll(same);
-    }
-    __syncthreads();
-    {
-        const int d = tid;
-        uint32_t c = 0;
-#pragma unroll
-        for (int w = 0; w < WPB; ++w) {
-            const uint32_t x = wh[w][d];
-            wh[w][d] = c;
-            c += x;
-        }
-        uint32_t *st = status + (size_t)tile * 256 + d;
-        __hip_atomic_store(st, (tile == 0 ? OS_PRE : OS_AGG) | c, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t lsd = block_scan_excl(c, sh, nullptr);
-        ls[d] = lsd;
-        uint32_t acc = 0;
-        if (tile > 0) {
-            uint32_t tt = tile - 1;
-            for (;;) {
-                const uint32_t v = __hip_atomic_load(status + (size_t)tt * 256 + d, __ATOMIC_RELAXED,
-                                                     __HIP_MEMORY_SCOPE_AGENT);
-                if ((v >> 30) == 0) {
-                    __builtin_amdgcn_s_sleep(1);
-                    continue;
-                }
-                acc += v & OS_VAL;
-                if (v & OS_PRE) break;
-                --tt;
-            }
-            __hip_atomic_store(st, OS_PRE | (acc + c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        gofs[d] = gexcl[d] + acc - lsd;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < OS_ITEMS; ++r) {
-        const uint32_t e = base + r * 64 + lane;
-        if (e < n) {
-            const uint32_t d = (kk[r] >> shift) & 255u;
-            const uint32_t pos = ls[d] + wh[wave][d] + rk[r];
-            sk[pos] = kk[r];
-            sv[pos] = vv[r];
-        }
-    }
-    __syncthreads();
-    const uint32_t cnt = min((uint32_t)OS_TILE, n - t0);
-#pragma unroll
-    for (int r = 0; r < OS_ITEMS; ++r) {
-        const uint32_t i = r * TB + tid;
-        if (i < cnt) {
-            const uint32_t k = sk[i];
-            const uint32_t dst = gofs[(k >> shift) & 255u] + i;
-            kout[dst] = k;
-            vout[dst] = sv[i];
-        }
-    }
-}
-
-nbkd_status onesweep_sort(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
-                          uint32_t n, int passes, hipStream_t s) {
-    const uint32_t ntiles = (n + OS_TILE - 1) / OS_TILE;
-    // [passes][256] histogram | [passes] tickets (padded to 64 words) | [passes][ntiles][256] status
-    const size_t words = (size_t)passes * 256 + 64 + (size_t)passes * ntiles * 256;
-    uint32_t *w = (uint32_t *)ws.get(WS_HIST, words * 4, s);
-    if (!w) return NBKD_ENOMEM;
-    NBKD_HIP(hipMemsetAsync(w, 0, words * 4, s));
-    uint32_t *ghist = w, *tickets = w + passes * 256, *status = tickets + 64;
-    const unsigned hb = (unsigned)std::min<uint32_t>((n + TB - 1) / TB, 2048);
-    os_hist_kernel<<<hb, TB, 0, s>>>(k0, n, passes, ghist);
-    os_scan_kernel<<<1, TB, 0, s>>>(ghist, passes);
-    for (int p = 0; p < passes; ++p) {
-        uint32_t *ki = (p & 1) ? k1 : k0, *vi = (p & 1) ? v1 : v0;
-        uint32_t *ko = (p & 1) ? k0 : k1, *vo = (p & 1) ? v0 : v1;
-        os_pass_kernel<<<ntiles, TB, 0, s>>>(ki, vi, n, 8 * p, ghist + p * 256, status +
-                                             (size_t)p * ntiles * 256, tickets + p, ko, vo);
-    }
-    NBKD_HIP(hipGetLastError());
-    return NBKD_OK;
-}
-
-// sorts (keys, vals) by the low `nbits` of keys, ceil(nbits/8) LSD passes
-// ping-ponging between (k0, v0) and (k1, v1); *vout = the sorted values
-nbkd_status radix_sort(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
-                       uint32_t n, int nbits, hipStream_t s, uint32_t **vout) {
-    *vout = v0;
-    if (n <= 1) return NBKD_OK;
-    {
-        static const bool old_sort = knob("NBKD_OLD_SORT") != nullptr; // A/B only
-        const int passes = (nbits + 7) / 8;
-        if (!old_sort && n < OS_VAL && passes <= OS_MAXP) {
-            *vout = (passes & 1) ? v1 : v0;
-            return onesweep_sort(ws, k0, v0, k1, v1, n, passes, s);
-        }
-    }
-    const uint32_t ntiles = (n + RS_TILE - 1) / RS_TILE;
-    uint32_t *hist = (uint32_t *)ws.get(WS_HIST, (size_t)256 * ntiles * 4, s);
-    if (!hist) return NBKD_ENOMEM;
-    const int passes = (nbits + 7) / 8;
-    *vout = (passes & 1) ? v1 : v0;
-    for (int p = 0; p < passes; ++p) {
-        const int shift = 8 * p;
-        uint32_t *ki = (p & 1) ? k1 : k0, *vi = (p & 1) ? v1 : v0;
-        uint32_t *ko = (p & 1) ? k0 : k1, *vo = (p & 1) ? v0 : v1;
-        rs_hist_kernel<<<ntiles, TB, 0, s>>>(ki, n, shift, ntiles, hist);
-        nbkd_status st = device_excl_scan(ws, hist, (uint64_t)256 * ntiles, s);
-        if (st) return st;
-        rs_scatter_kernel<<<ntiles, TB, 0, s>>>(ki, vi, n, shift, ntiles, hist, ko, vo);
-        NBKD_HIP(hipGetLastError());
-    }
-    return NBKD_OK;
-}
-
 // ------------------------------------------------------------------ reference-exact traversal
 // One lane per query, replaying KDTreeQuery::compute (kdtree_impl.hpp:226-268)
 // step for step: near child first (left unless q[dim] > split), near visited iff
@@ -1012,8 +664,8 @@ int key_bits(const Tree &t) {
 constexpr int KNN_PACKET_KMAX = 1024;
 // internal flag (never a caller's): this knn_locked call is an nbkd_query_knn
 // whose CALLER asked for device rows, so it may write the nbkd_set_kth_out
-// array (host_pipeline adds NBKD_OUTPUT_DEVICE to its batch calls,
-// and kth_locked's k > 1024 rows go to scratch; neither may touch it)
+// array (host_pipeline's batch calls write device slots, and
+// kth_locked's k > 1024 rows go to scratch; neither may touch it)
 constexpr uint32_t KNN_SIDE_OK = 0x80000000u;
 
 #ifndef NBKD_KNN_CHILD_TH
@@ -1187,6 +839,92 @@ nbkd_status stage_queries(Workspace &ws, const float *q, uint64_t m, uint32_t fl
     return NBKD_OK;
 }
 
+// What a radius-family worker needs of its m device queries dq: their kd
+// order (the self order when they are the tree's build array, else the
+// bucketing descent and sort) and, with `outside` on a periodic tree, the list
+// of the queries outside [0, L]^3, for which every point is tested.  The
+// list's length stays in device memory, at count.
+struct QueryPlan {
+    uint32_t *order;
+    uint32_t *list, *count; // nullptr: no list (not periodic, or not asked for)
+};
+nbkd_status plan_queries(const Tree &t, Workspace &ws, const float *dq, uint32_t m, bool outside,
+                         QueryPlan &p, hipStream_t s) {
+    p = QueryPlan{nullptr, nullptr, nullptr};
+    const nbkd_status rc = self_query(t, dq, m, NBKD_INPUT_DEVICE)
+                               ? self_order(t, ws, m, p.order, s)
+                               : sort_queries(t, ws, dq, m, p.order, s);
+    if (rc || !outside || !t.periodic) return rc;
+    p.list = (uint32_t *)ws.get(WS_LIST, (size_t)m * 8 + 16, s);
+    if (!p.list) return NBKD_ENOMEM;
+    p.count = p.list + m;
+    NBKD_HIP(hipMemsetAsync(p.count, 0, 4, s));
+    outside_box_kernel<<<(m + TB - 1) / TB, TB, 0, s>>>(dq, m, t.box, p.list, p.count);
+    return NBKD_OK;
+}
+
+// The work counters of one worker call (WS_STATS, nullptr while the counters
+// are off): zeroed before its kernels, added to the thread's totals after them
+nbkd_status stats_begin(Workspace &ws, unsigned long long *&stats, hipStream_t s) {
+    stats = nullptr;
+    if (!stats_enabled()) return NBKD_OK;
+    stats = (unsigned long long *)ws.get(WS_STATS, NBKD_NSTATS * 8, s);
+    if (!stats) return NBKD_ENOMEM;
+    NBKD_HIP(hipMemsetAsync(stats, 0, NBKD_NSTATS * 8, s));
+    return NBKD_OK;
+}
+nbkd_status stats_end(const unsigned long long *stats, hipStream_t s) {
+    if (!stats) return NBKD_OK;
+    uint64_t h[NBKD_NSTATS];
+    NBKD_HIP(hipMemcpyAsync(h, stats, NBKD_NSTATS * 8, hipMemcpyDeviceToHost, s));
+    NBKD_HIP(hipStreamSynchronize(s));
+    stats_add(h);
+    return NBKD_OK;
+}
+
+// A per-point input array (values, masses) on the device: the caller's own
+// when it is device memory or absent, else uploaded to WS_VALS; the caller's
+// array has been read when this returns
+nbkd_status upload_per_point(Workspace &ws, const float *&a, size_t bytes, bool in_dev,
+                             hipStream_t s) {
+    if (!a || in_dev) return NBKD_OK;
+    float *up = (float *)ws.get(WS_VALS, bytes, s);
+    if (!up) return NBKD_ENOMEM;
+    NBKD_HIP(hipMemcpyAsync(up, a, bytes, hipMemcpyHostToDevice, s));
+    NBKD_HIP(hipStreamSynchronize(s));
+    a = up;
+    return NBKD_OK;
+}
+
+// The per-point values (n, nv) once per call, in tree order: vt[p] =
+// values[row(p)], 1 without values (WS_VT); the gather is timed as `scope`
+nbkd_status tree_order_values(const Tree &t, Workspace &ws, const float *values, int nv,
+                              bool in_dev, const char *scope, const float *&vt, hipStream_t s) {
+    const nbkd_status rc = upload_per_point(ws, values, (size_t)t.n * (size_t)nv * 4, in_dev, s);
+    if (rc) return rc;
+    float *out = (float *)ws.get(WS_VT, (size_t)t.n8 * (size_t)nv * 4, s);
+    if (!out) return NBKD_ENOMEM;
+    TimedScope ts(scope, s);
+    launch_ball_sum_gather(t, values, nv, out, s);
+    NBKD_HIP(hipGetLastError());
+    vt = out;
+    return NBKD_OK;
+}
+
+// The slice [b0, b0 + nb) of a per-query side array (h, scale; nullptr: none)
+// for one batch on stream st: the caller's own when it is device memory, else
+// uploaded to WS_HRAD
+nbkd_status batch_slice(Workspace &ws, const float *a, uint64_t b0, uint64_t nb, bool in_dev,
+                        const float *&d, hipStream_t st) {
+    d = a ? a + b0 : nullptr;
+    if (!a || in_dev) return NBKD_OK;
+    float *hb = (float *)ws.get(WS_HRAD, (size_t)nb * 4, st);
+    if (!hb) return NBKD_ENOMEM;
+    NBKD_HIP(hipMemcpyAsync(hb, a + b0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    d = hb;
+    return NBKD_OK;
+}
+
 } // namespace
 
 // Candidate-column budget per collect/select batch: NBKD_CAND_BYTES, else the
@@ -1214,17 +952,6 @@ uint64_t cand_budget(bool *is_auto) {
     return b;
 }
 
-// LSD radix sort of (key, value) pairs for other translation units (deposit.hip)
-nbkd_status sort_pairs(Workspace &ws, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1,
-                       uint32_t n, int nbits, hipStream_t s, uint32_t **vout) {
-    return radix_sort(ws, k0, v0, k1, v1, n, nbits, s, vout);
-}
-
-// the exclusive scan for other translation units (group.hip)
-nbkd_status excl_scan(Workspace &ws, uint32_t *a, uint64_t n, hipStream_t s) {
-    return device_excl_scan(ws, a, n, s);
-}
-
 namespace {
 
 bool collect_disabled() {
@@ -1235,17 +962,18 @@ bool collect_disabled() {
     return off;
 }
 
-// out_i == nullptr: k-th distance only (out_d: m floats); the caller
+// Device in, device out: the (m, k) rows of m device queries dq into the
+// device arrays dd / di; every placement of a caller's arrays is the entry
+// points' business (run_placed).  Of flags only NBKD_SQUARED and KNN_SIDE_OK
+// are read.
+// di == nullptr: k-th distance only (dd: m floats); the caller
 // (query_kth) uses it only where the collect/select path runs
-nbkd_status knn_locked(const Tree &t, Workspace &ws, const float *q, uint64_t m, int k, float *out_d,
-                       uint32_t *out_i, uint32_t flags, hipStream_t s) {
+nbkd_status knn_locked(const Tree &t, Workspace &ws, const float *dq, uint64_t m, int k, float *dd,
+                       uint32_t *di, uint32_t flags, hipStream_t s) {
     const uint32_t mm = (uint32_t)m;
-    const bool kth_only = out_i == nullptr;
+    const bool kth_only = di == nullptr;
     const bool sq = (flags & NBKD_SQUARED) != 0;
-    const size_t row_words = kth_only ? 1 : (size_t)k;
-    const float *dq = nullptr;
-    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
-    if (rc) return rc;
+    nbkd_status rc = NBKD_OK;
     // the collect / select path needs the sub-leaf groups (every non-empty
     // tree has them); k > 1024 and the empty tree take the exact kernel
     const bool packet = k <= KNN_PACKET_KMAX && t.ginfo != nullptr;
@@ -1257,7 +985,7 @@ nbkd_status knn_locked(const Tree &t, Workspace &ws, const float *q, uint64_t m,
     }
     uint32_t *ord = nullptr;
     // self queries: tree order, seeds per position (tgp) for the first pass
-    const bool self = packet && tg && self_query(t, q, m, flags);
+    const bool self = packet && tg && self_query(t, dq, m, NBKD_INPUT_DEVICE);
     float *tgp = nullptr;
     if (self) {
         tgp = (float *)ws.get(WS_KEYS, (size_t)mm * 4, s);
@@ -1274,23 +1002,12 @@ nbkd_status knn_locked(const Tree &t, Workspace &ws, const float *q, uint64_t m,
     // (self_order = 0), the lane selects write it (select_block indexes it by
     // query id), the exact kernel's rows and every row at k > 64 (including
     // k > 1024, no packet path) are copied by kth_patch_kernel below
-    const bool own_rows = (flags & NBKD_INPUT_DEVICE) && q != nullptr && q == t.src && m > 0 &&
-                          m <= t.n;
+    const bool own_rows = dq != nullptr && dq == t.src && m > 0 && m <= t.n;
     float *const ks = own_rows && !kth_only && (flags & KNN_SIDE_OK) && t.kth_side &&
                               m <= t.kth_side_cap ? t.kth_side : nullptr;
-    float *dd = out_d;
-    uint32_t *di = out_i;
-    if (!(flags & NBKD_OUTPUT_DEVICE)) {
-        dd = (float *)ws.get(WS_OUTD, m * row_words * 4, s);
-        di = kth_only ? nullptr : (uint32_t *)ws.get(WS_OUTI, m * (size_t)k * 4, s);
-        if (!dd || (!di && !kth_only)) return NBKD_ENOMEM;
-    }
     unsigned long long *stats = nullptr;
-    if (stats_enabled()) {
-        stats = (unsigned long long *)ws.get(WS_STATS, NBKD_NSTATS * 8, s);
-        if (!stats) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(stats, 0, NBKD_NSTATS * 8, s));
-    }
+    rc = stats_begin(ws, stats, s);
+    if (rc) return rc;
     // queries the packet kernel cannot answer exactly go through the
     // reference-exact lane-per-query kernel: periodic queries outside [0, L]^3
     // and queries whose seed radius held fewer than k points
@@ -1497,19 +1214,7 @@ nbkd_status knn_locked(const Tree &t, Workspace &ws, const float *q, uint64_t m,
             NBKD_HIP(hipGetLastError());
         }
     }
-    if (stats) {
-        uint64_t h[NBKD_NSTATS];
-        NBKD_HIP(hipMemcpyAsync(h, stats, NBKD_NSTATS * 8, hipMemcpyDeviceToHost, s));
-        NBKD_HIP(hipStreamSynchronize(s));
-        stats_add(h);
-    }
-    if (!(flags & NBKD_OUTPUT_DEVICE)) {
-        NBKD_HIP(hipMemcpyAsync(out_d, dd, m * row_words * 4, hipMemcpyDeviceToHost, s));
-        if (!kth_only)
-            NBKD_HIP(hipMemcpyAsync(out_i, di, m * (size_t)k * 4, hipMemcpyDeviceToHost, s));
-        NBKD_HIP(hipStreamSynchronize(s));
-    }
-    return NBKD_OK;
+    return stats_end(stats, s);
 }
 
 nbkd_status knn_args(int k, uint64_t m) {
@@ -1558,6 +1263,8 @@ uint64_t host_batch(size_t bytes_per_query, uint64_t m) {
     return std::min<uint64_t>(hb, m);
 }
 
+// run(dq, b0, nb, outs, stream): the nb device queries dq of the batch that
+// starts at query b0, into the device arrays outs[0 .. nout)
 template <typename Run>
 nbkd_status host_pipeline(Workspace &ws, const float *q, uint64_t m, uint32_t flags, int nout,
                           const size_t *obytes, void *const *outs, size_t scratch_per_q, Run run,
@@ -1639,7 +1346,7 @@ nbkd_status host_pipeline(Workspace &ws, const float *q, uint64_t m, uint32_t fl
                 o[j] = out_dev ? (void *)((char *)outs[j] + b0 * obytes[j]) : oslot[b][j];
             // device output slot b is free once batch i-2's results left it
             if (!out_dev && out_rec[b]) NBKD_PIPE(hipStreamWaitEvent(s, ev_out[b], 0));
-            rc = run(dq, nb, o, s);
+            rc = run(dq, b0, nb, o, s);
             if (rc) break;
             NBKD_PIPE(hipEventRecord(ev_comp[b], s));
             comp_rec[b] = true;
@@ -1677,6 +1384,33 @@ drain:
     return NBKD_OK;
 }
 
+// The per-query output arrays of a call, in the order a batch's slices reach
+// `run`.  add() returns the array's slot, or -1 for an absent (nullptr) output,
+// which takes none; out_at() is the way back.
+struct OutList {
+    int n = 0;
+    size_t bytes[2] = {0, 0};
+    void *ptr[2] = {nullptr, nullptr};
+    int add(void *p, size_t bytes_per_query) {
+        if (!p) return -1;
+        bytes[n] = bytes_per_query;
+        ptr[n] = p;
+        return n++;
+    }
+};
+static void *out_at(void *const *outs, int i) { return i >= 0 ? outs[i] : nullptr; }
+
+// The m queries of an entry point through `run` (host_pipeline's callback):
+// queries and outputs all in device memory are one direct run over the
+// caller's own arrays; every other placement streams in batches
+template <typename Run>
+nbkd_status run_placed(Workspace &ws, const float *q, uint64_t m, uint32_t flags, const OutList &o,
+                       size_t scratch_per_q, Run run, hipStream_t s) {
+    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
+    if ((flags & dev_io) == dev_io) return run(q, (uint64_t)0, m, o.ptr, s);
+    return host_pipeline(ws, q, m, flags, o.n, o.bytes, o.ptr, scratch_per_q, run, s);
+}
+
 // device scratch per query of one batch call that no budget bounds: the
 // order / seed / list / failure buffers (~40 B), plus the full rows the k-th
 // distance takes where the collect / select path does not run (k > 1024, the
@@ -1697,22 +1431,26 @@ nbkd_status query_knn(const Tree &t, const float *q, uint64_t m, int k, float *o
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
+    // only a caller who asked for device rows of device queries gets the
+    // nbkd_set_kth_out array written (KNN_SIDE_OK)
     const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    flags &= ~KNN_SIDE_OK;
-    if ((flags & dev_io) == dev_io)
-        return knn_locked(t, ws, q, m, k, out_d, out_i, flags | KNN_SIDE_OK, s);
-    const size_t ob[2] = {(size_t)k * 4, (size_t)k * 4};
-    void *const outs[2] = {out_d, out_i};
-    return host_pipeline(ws, q, m, flags, 2, ob, outs, knn_scratch_per_query(t, k, false),
-                         [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
-                             return knn_locked(t, ws, dq, nb, k, (float *)o[0], (uint32_t *)o[1],
-                                               flags | dev_io, st);
-                         }, s);
+    const uint32_t kflags =
+        (flags & NBKD_SQUARED) | ((flags & dev_io) == dev_io ? KNN_SIDE_OK : 0u);
+    OutList o;
+    o.add(out_d, (size_t)k * 4);
+    o.add(out_i, (size_t)k * 4);
+    return run_placed(ws, q, m, flags, o, knn_scratch_per_query(t, k, false),
+                      [&](const float *dq, uint64_t, uint64_t nb, void *const *b, hipStream_t st) {
+                          return knn_locked(t, ws, dq, nb, k, (float *)b[0], (uint32_t *)b[1],
+                                            kflags, st);
+                      }, s);
 }
 
-// device in, device out: the k-th distances of m queries
+// device in, device out: the k-th distances of m device queries into the
+// device array out_d (squared with sq)
 static nbkd_status kth_locked(const Tree &t, Workspace &ws, const float *dq, uint64_t m, int k,
-                              float *out_d, uint32_t flags, hipStream_t s) {
+                              float *out_d, bool sq, hipStream_t s) {
+    const uint32_t flags = sq ? NBKD_SQUARED : 0u;
     // the collect/select path writes the k-th distance alone; elsewhere the
     // rows go to scratch and column k-1 is copied out
     if (k <= KNN_PACKET_KMAX && t.ginfo && seed_params(t, k).on && !collect_disabled())
@@ -1735,72 +1473,35 @@ nbkd_status query_kth(const Tree &t, const float *q, uint64_t m, int k, float *o
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    if ((flags & dev_io) == dev_io) return kth_locked(t, ws, q, m, k, out_d, flags, s);
-    const size_t ob[1] = {4};
-    void *const outs[1] = {out_d};
-    return host_pipeline(ws, q, m, flags, 1, ob, outs, knn_scratch_per_query(t, k, true),
-                         [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
-                             return kth_locked(t, ws, dq, nb, k, (float *)o[0], flags | dev_io, st);
-                         }, s);
+    const bool sq = (flags & NBKD_SQUARED) != 0;
+    OutList o;
+    o.add(out_d, 4);
+    return run_placed(ws, q, m, flags, o, knn_scratch_per_query(t, k, true),
+                      [&](const float *dq, uint64_t, uint64_t nb, void *const *b, hipStream_t st) {
+                          return kth_locked(t, ws, dq, nb, k, (float *)b[0], sq, st);
+                      }, s);
 }
 
-// the radius count of m device queries (count into out_count: device memory
-// when NBKD_OUTPUT_DEVICE, else staged)
-static nbkd_status ball_common(const Tree &t, Workspace &ws, const float *q, uint64_t m, float r,
-                               uint32_t *out_count, uint32_t flags, hipStream_t s) {
-    if (m >= (1ull << 32)) {
-        set_error("more than 2^32 - 1 queries per call are not supported");
-        return NBKD_EINVAL;
-    }
+// device in, device out: the radius counts of m < 2^32 device queries dq into
+// the device array cnt
+static nbkd_status ball_common(const Tree &t, Workspace &ws, const float *dq, uint64_t m, float r,
+                               uint32_t *cnt, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    const float *dq = nullptr;
-    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
-    if (rc) return rc;
-    uint32_t *ord = nullptr;
-    rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                    : sort_queries(t, ws, dq, mm, ord, s);
+    QueryPlan p;
+    nbkd_status rc = plan_queries(t, ws, dq, mm, true, p, s);
     if (rc) return rc;
     const float r2 = radius_thr(r);
-    // periodic queries outside [0, L]^3: listed (their count stays in device
-    // memory), every point tested for them
-    uint32_t *list = nullptr;
-    if (t.periodic) {
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
-        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
-    }
     unsigned long long *stats = nullptr;
-    if (stats_enabled()) {
-        stats = (unsigned long long *)ws.get(WS_STATS, NBKD_NSTATS * 8, s);
-        if (!stats) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(stats, 0, NBKD_NSTATS * 8, s));
-    }
-    uint32_t *cnt = out_count;
-    const bool dev_out = flags & NBKD_OUTPUT_DEVICE;
-    if (!dev_out) {
-        cnt = (uint32_t *)ws.get(WS_COUNT, m * 4, s);
-        if (!cnt) return NBKD_ENOMEM;
-    }
+    rc = stats_begin(ws, stats, s);
+    if (rc) return rc;
     {
         TimedScope ts("ball_count", s);
-        launch_ball_packet(t, dq, ord, mm, r2, cnt, nullptr, nullptr, stats, s);
-        if (list) launch_ball_outside_dev(t, dq, list, list + mm, r2, cnt, s);
+        launch_ball_packet(t, dq, p.order, mm, r2, cnt, nullptr, nullptr, stats, s);
+        if (p.list) launch_ball_outside_dev(t, dq, p.list, p.count, r2, cnt, s);
         NBKD_HIP(hipGetLastError());
     }
-    if (stats) {
-        uint64_t h[NBKD_NSTATS];
-        NBKD_HIP(hipMemcpyAsync(h, stats, NBKD_NSTATS * 8, hipMemcpyDeviceToHost, s));
-        NBKD_HIP(hipStreamSynchronize(s));
-        stats_add(h);
-    }
-    if (!dev_out) {
-        NBKD_HIP(hipMemcpyAsync(out_count, cnt, m * 4, hipMemcpyDeviceToHost, s));
-        NBKD_HIP(hipStreamSynchronize(s));
-    }
-    return NBKD_OK;
+    return stats_end(stats, s);
 }
 
 nbkd_status query_ball_count(const Tree &t, const float *q, uint64_t m, float r,
@@ -1814,43 +1515,29 @@ nbkd_status query_ball_count(const Tree &t, const float *q, uint64_t m, float r,
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    if ((flags & dev_io) == dev_io)
-        return ball_common(t, ws, q, m, r, out_count, flags, s);
-    const size_t ob[1] = {4};
-    void *const outs[1] = {out_count};
-    return host_pipeline(ws, q, m, flags, 1, ob, outs, 40,
-                         [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
-                             return ball_common(t, ws, dq, nb, r, (uint32_t *)o[0], flags | dev_io,
-                                                st);
-                         }, s);
+    OutList o;
+    o.add(out_count, 4);
+    return run_placed(ws, q, m, flags, o, 40,
+                      [&](const float *dq, uint64_t, uint64_t nb, void *const *b, hipStream_t st) {
+                          return ball_common(t, ws, dq, nb, r, (uint32_t *)b[0], st);
+                      }, s);
 }
 
-// the kernel-weighted sums of m device queries with device radii into device
-// outputs (either may be nullptr); vt = the values in tree order
+// device in, device out: the kernel-weighted sums of m device queries q with
+// device radii h into device outputs (either may be nullptr); vt = the values
+// in tree order
 static nbkd_status ball_sum_common(const Tree &t, Workspace &ws, const float *q, const float *h,
                                    uint64_t m, const float *vt, int nv, int kernel,
-                                   float *out_sum, uint32_t *out_count, uint32_t flags,
-                                   hipStream_t s) {
+                                   float *out_sum, uint32_t *out_count, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    uint32_t *ord = nullptr;
-    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                                : sort_queries(t, ws, q, mm, ord, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, q, mm, true, p, s);
     if (rc) return rc;
-    // periodic queries outside [0, L]^3: listed (the length stays in device
-    // memory), every point tested for them
-    uint32_t *list = nullptr;
-    if (t.periodic) {
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
-        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(q, mm, t.box, list, list + mm);
-    }
     TimedScope ts("ball_sum", s);
-    launch_ball_sum(t, q, h, ord, mm, vt, nv, kernel, out_sum, out_count, s);
-    if (list)
-        launch_ball_sum_outside_dev(t, q, h, list, list + mm, vt, nv, kernel, out_sum, out_count,
+    launch_ball_sum(t, q, h, p.order, mm, vt, nv, kernel, out_sum, out_count, s);
+    if (p.list)
+        launch_ball_sum_outside_dev(t, q, h, p.list, p.count, vt, nv, kernel, out_sum, out_count,
                                     s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
@@ -1863,57 +1550,21 @@ nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const floa
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
     const bool in_dev = (flags & NBKD_INPUT_DEVICE) != 0;
-    // the values once per call: uploaded when they are host memory, then
-    // gathered into tree order (vt[p] = values[row(p)], 1 without values)
-    const float *dvals = values;
-    if (values && !in_dev) {
-        const size_t vb = (size_t)t.n * (size_t)nv * 4;
-        float *up = (float *)ws.get(WS_VALS, vb, s);
-        if (!up) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemcpyAsync(up, values, vb, hipMemcpyHostToDevice, s));
-        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
-        dvals = up;
-    }
-    float *vt = (float *)ws.get(WS_VT, (size_t)t.n8 * (size_t)nv * 4, s);
-    if (!vt) return NBKD_ENOMEM;
-    {
-        TimedScope ts("ball_sum_gather", s);
-        launch_ball_sum_gather(t, dvals, nv, vt, s);
-        NBKD_HIP(hipGetLastError());
-    }
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    if ((flags & dev_io) == dev_io)
-        return ball_sum_common(t, ws, q, h, m, vt, nv, kernel, out_sum, out_count, flags, s);
-    // host arrays stream in batches; each batch's slice of h follows its
-    // queries (the pipeline hands over the batch, not its offset: b0 runs along)
-    size_t ob[2];
-    void *outs[2];
-    int nout = 0;
-    const int isum = out_sum ? nout : -1;
-    if (out_sum) {
-        ob[nout] = (size_t)nv * 4;
-        outs[nout++] = out_sum;
-    }
-    const int icnt = out_count ? nout : -1;
-    if (out_count) {
-        ob[nout] = 4;
-        outs[nout++] = out_count;
-    }
-    uint64_t b0 = 0;
-    const nbkd_status rc = host_pipeline(
-        ws, q, m, flags, nout, ob, outs, 44,
-        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
-            const float *dh = h + b0;
-            if (!in_dev) {
-                float *hb = (float *)ws.get(WS_HRAD, (size_t)nb * 4, st);
-                if (!hb) return NBKD_ENOMEM;
-                NBKD_HIP(hipMemcpyAsync(hb, h + b0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
-                dh = hb;
-            }
-            b0 += nb;
-            return ball_sum_common(t, ws, dq, dh, nb, vt, nv, kernel,
-                                   isum >= 0 ? (float *)o[isum] : nullptr,
-                                   icnt >= 0 ? (uint32_t *)o[icnt] : nullptr, flags | dev_io, st);
+    const float *vt = nullptr;
+    nbkd_status rc = tree_order_values(t, ws, values, nv, in_dev, "ball_sum_gather", vt, s);
+    if (rc) return rc;
+    // each batch's slice of h follows its queries
+    OutList o;
+    const int isum = o.add(out_sum, (size_t)nv * 4), icnt = o.add(out_count, 4);
+    rc = run_placed(
+        ws, q, m, flags, o, 44,
+        [&](const float *dq, uint64_t b0, uint64_t nb, void *const *b,
+            hipStream_t st) -> nbkd_status {
+            const float *dh = nullptr;
+            const nbkd_status rb = batch_slice(ws, h, b0, nb, in_dev, dh, st);
+            if (rb) return rb;
+            return ball_sum_common(t, ws, dq, dh, nb, vt, nv, kernel, (float *)out_at(b, isum),
+                                   (uint32_t *)out_at(b, icnt), st);
         }, s);
     if (rc) return rc;
     // the caller's h (pageable memory) has been read when the call returns
@@ -1921,30 +1572,21 @@ nbkd_status query_ball_sum(const Tree &t, const float *q, uint64_t m, const floa
     return NBKD_OK;
 }
 
-// the per-bin sums of m device queries with device scales (or nullptr) into
-// the device array out_sum (m, nr, nv); vt = the values in tree order
+// device in, device out: the per-bin sums of m device queries q with device
+// scales (or nullptr) into the device array out_sum (m, nr, nv); vt = the
+// values in tree order
 static nbkd_status profile_common(const Tree &t, Workspace &ws, const float *q, const float *scale,
                                   uint64_t m, const ProfRadii &R, int nr, const float *vt, int nv,
-                                  float *out_sum, uint32_t flags, hipStream_t s) {
+                                  float *out_sum, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    uint32_t *ord = nullptr;
-    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                                : sort_queries(t, ws, q, mm, ord, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, q, mm, true, p, s);
     if (rc) return rc;
-    // periodic queries outside [0, L]^3: listed (the length stays in device
-    // memory), every point tested for them
-    uint32_t *list = nullptr;
-    if (t.periodic) {
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
-        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(q, mm, t.box, list, list + mm);
-    }
     TimedScope ts("ball_profile", s);
-    launch_ball_profile(t, q, scale, ord, mm, R, nr, vt, nv, out_sum, s);
-    if (list)
-        launch_ball_profile_outside_dev(t, q, scale, list, list + mm, R, nr, vt, nv, out_sum, s);
+    launch_ball_profile(t, q, scale, p.order, mm, R, nr, vt, nv, out_sum, s);
+    if (p.list)
+        launch_ball_profile_outside_dev(t, q, scale, p.list, p.count, R, nr, vt, nv, out_sum, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
@@ -1960,45 +1602,20 @@ nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const 
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
     const bool in_dev = (flags & NBKD_INPUT_DEVICE) != 0;
-    // the values once per call: uploaded when they are host memory, then
-    // gathered into tree order (vt[p] = values[row(p)], 1 without values)
-    const float *dvals = values;
-    if (values && !in_dev) {
-        const size_t vb = (size_t)t.n * (size_t)nv * 4;
-        float *up = (float *)ws.get(WS_VALS, vb, s);
-        if (!up) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemcpyAsync(up, values, vb, hipMemcpyHostToDevice, s));
-        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
-        dvals = up;
-    }
-    float *vt = (float *)ws.get(WS_VT, (size_t)t.n8 * (size_t)nv * 4, s);
-    if (!vt) return NBKD_ENOMEM;
-    {
-        TimedScope ts("ball_profile_gather", s);
-        launch_ball_sum_gather(t, dvals, nv, vt, s);
-        NBKD_HIP(hipGetLastError());
-    }
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    if ((flags & dev_io) == dev_io)
-        return profile_common(t, ws, q, scale, m, R, nr, vt, nv, out_sum, flags, s);
-    // host arrays stream in batches; each batch's slice of scale follows its
-    // queries (the pipeline hands over the batch, not its offset: b0 runs along)
-    const size_t ob[1] = {(size_t)nr * (size_t)nv * 4};
-    void *const outs[1] = {out_sum};
-    uint64_t b0 = 0;
-    const nbkd_status rc = host_pipeline(
-        ws, q, m, flags, 1, ob, outs, 44,
-        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
-            const float *dsc = scale ? scale + b0 : nullptr;
-            if (scale && !in_dev) {
-                float *hb = (float *)ws.get(WS_HRAD, (size_t)nb * 4, st);
-                if (!hb) return NBKD_ENOMEM;
-                NBKD_HIP(hipMemcpyAsync(hb, scale + b0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
-                dsc = hb;
-            }
-            b0 += nb;
-            return profile_common(t, ws, dq, dsc, nb, R, nr, vt, nv, (float *)o[0], flags | dev_io,
-                                  st);
+    const float *vt = nullptr;
+    nbkd_status rc = tree_order_values(t, ws, values, nv, in_dev, "ball_profile_gather", vt, s);
+    if (rc) return rc;
+    // each batch's slice of scale follows its queries
+    OutList o;
+    o.add(out_sum, (size_t)nr * (size_t)nv * 4);
+    rc = run_placed(
+        ws, q, m, flags, o, 44,
+        [&](const float *dq, uint64_t b0, uint64_t nb, void *const *b,
+            hipStream_t st) -> nbkd_status {
+            const float *dsc = nullptr;
+            const nbkd_status rb = batch_slice(ws, scale, b0, nb, in_dev, dsc, st);
+            if (rb) return rb;
+            return profile_common(t, ws, dq, dsc, nb, R, nr, vt, nv, (float *)b[0], st);
         }, s);
     if (rc) return rc;
     // the caller's scale (pageable memory) has been read when the call returns
@@ -2006,27 +1623,27 @@ nbkd_status query_ball_profile(const Tree &t, const float *q, uint64_t m, const 
     return NBKD_OK;
 }
 
-// the potentials and accelerations of m device queries into device outputs
-// (either may be nullptr); rec = the node moments, mt = the masses in tree
-// order, table = the device Ewald table (periodic trees) or nullptr
+// device in, device out: the potentials and accelerations of m device queries
+// q into device outputs (either may be nullptr); rec = the node moments, mt =
+// the masses in tree order, table = the device Ewald table (periodic trees) or
+// nullptr.  The order alone: the Ewald walk gives outside queries NaNs itself.
 static nbkd_status gravity_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
                                   const void *rec, const void *table, const float *mt, float th2,
-                                  float eps2, float *out_phi, float *out_acc, uint32_t flags,
-                                  hipStream_t s) {
+                                  float eps2, float *out_phi, float *out_acc, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    uint32_t *ord = nullptr;
-    nbkd_status rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                                : sort_queries(t, ws, q, mm, ord, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, q, mm, false, p, s);
     if (rc) return rc;
     if (table) {
         TimedScope ts("gravity_ewald_walk", s);
-        launch_gravity_ewald_walk(t, rec, table, q, ord, mm, mt, th2, eps2, out_phi, out_acc, s);
+        launch_gravity_ewald_walk(t, rec, table, q, p.order, mm, mt, th2, eps2, out_phi, out_acc,
+                                  s);
         NBKD_HIP(hipGetLastError());
         return NBKD_OK;
     }
     TimedScope ts("gravity_walk", s);
-    launch_gravity_walk(t, rec, q, ord, mm, mt, th2, eps2, out_phi, out_acc, s);
+    launch_gravity_walk(t, rec, q, p.order, mm, mt, th2, eps2, out_phi, out_acc, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
@@ -2054,15 +1671,10 @@ static nbkd_status gravity_call(const Tree &t, const float *q, uint64_t m, const
     // the masses once per call: uploaded when they are host memory, gathered
     // into tree order (mt[p] = mass[row(p)], 1 without masses, 0 at the padding
     // positions), then the node moments from them
+    // (tree_order_values is not used: the gather is timed with the moments)
     const float *dmass = mass;
-    if (mass && !in_dev) {
-        const size_t vb = (size_t)t.n * 4;
-        float *up = (float *)ws.get(WS_VALS, vb, s);
-        if (!up) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemcpyAsync(up, mass, vb, hipMemcpyHostToDevice, s));
-        NBKD_HIP(hipStreamSynchronize(s)); // the caller's array has been read
-        dmass = up;
-    }
+    const nbkd_status rc = upload_per_point(ws, dmass, (size_t)t.n * 4, in_dev, s);
+    if (rc) return rc;
     float *mt = (float *)ws.get(WS_VT, (size_t)t.n8 * 4, s);
     void *scratch = ws.get(WS_GRAV, gravity_scratch_bytes(t), s);
     if (!mt || !scratch) return NBKD_ENOMEM;
@@ -2074,28 +1686,13 @@ static nbkd_status gravity_call(const Tree &t, const float *q, uint64_t m, const
         NBKD_HIP(hipGetLastError());
     }
     const float th2 = theta * theta, eps2 = eps * eps;
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    if ((flags & dev_io) == dev_io)
-        return gravity_common(t, ws, q, m, rec, table, mt, th2, eps2, out_phi, out_acc, flags, s);
-    size_t ob[2];
-    void *outs[2];
-    int nout = 0;
-    const int iphi = out_phi ? nout : -1;
-    if (out_phi) {
-        ob[nout] = 4;
-        outs[nout++] = out_phi;
-    }
-    const int iacc = out_acc ? nout : -1;
-    if (out_acc) {
-        ob[nout] = 12;
-        outs[nout++] = out_acc;
-    }
-    return host_pipeline(
-        ws, q, m, flags, nout, ob, outs, 40,
-        [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) -> nbkd_status {
+    OutList o;
+    const int iphi = o.add(out_phi, 4), iacc = o.add(out_acc, 12);
+    return run_placed(
+        ws, q, m, flags, o, 40,
+        [&](const float *dq, uint64_t, uint64_t nb, void *const *b, hipStream_t st) {
             return gravity_common(t, ws, dq, nb, rec, table, mt, th2, eps2,
-                                  iphi >= 0 ? (float *)o[iphi] : nullptr,
-                                  iacc >= 0 ? (float *)o[iacc] : nullptr, flags | dev_io, st);
+                                  (float *)out_at(b, iphi), (float *)out_at(b, iacc), st);
         }, s);
 }
 
@@ -2116,33 +1713,20 @@ nbkd_status query_gravity_ewald(const Tree &t, const float *q, uint64_t m, const
     return gravity_call(t, q, m, mass, theta, eps, table, out_phi, out_acc, flags, s);
 }
 
-// the radius histogram of m device queries: rows into the device array
-// out_counts (or nullptr), column sums added to the device counters tot (or
-// nullptr)
-static nbkd_status hist_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
+// device in, device out: the radius histogram of m device queries dq: rows
+// into the device array out_counts (or nullptr), column sums added to the
+// device counters tot (or nullptr)
+static nbkd_status hist_common(const Tree &t, Workspace &ws, const float *dq, uint64_t m,
                                const HistThr &thr, int nr, uint32_t *out_counts,
-                               unsigned long long *tot, uint32_t flags, hipStream_t s) {
+                               unsigned long long *tot, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    const float *dq = nullptr;
-    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, dq, mm, true, p, s);
     if (rc) return rc;
-    uint32_t *ord = nullptr;
-    rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                    : sort_queries(t, ws, dq, mm, ord, s);
-    if (rc) return rc;
-    // periodic queries outside [0, L]^3: listed (the length stays in device
-    // memory), every point tested for them
-    uint32_t *list = nullptr;
-    if (t.periodic) {
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
-        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
-    }
     TimedScope ts("ball_hist", s);
-    launch_ball_hist(t, dq, ord, mm, thr, nr, out_counts, tot, s);
-    if (list) launch_ball_hist_outside_dev(t, dq, list, list + mm, thr, nr, out_counts, tot, s);
+    launch_ball_hist(t, dq, p.order, mm, thr, nr, out_counts, tot, s);
+    if (p.list) launch_ball_hist_outside_dev(t, dq, p.list, p.count, thr, nr, out_counts, tot, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
@@ -2174,20 +1758,13 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
     }
     // no rows wanted: nothing leaves the device but the totals
     if (!out_counts) flags |= NBKD_OUTPUT_DEVICE;
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    nbkd_status rc;
-    if ((flags & dev_io) == dev_io) {
-        rc = hist_common(t, ws, q, m, thr, nr, out_counts, tot, flags, s);
-    } else {
-        const size_t ob[1] = {(size_t)nr * 4};
-        void *const outs[1] = {out_counts};
-        rc = host_pipeline(ws, q, m, flags, out_counts ? 1 : 0, ob, outs, 40,
-                           [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
-                               return hist_common(t, ws, dq, nb, thr, nr,
-                                                  out_counts ? (uint32_t *)o[0] : nullptr, tot,
-                                                  flags | dev_io, st);
-                           }, s);
-    }
+    OutList o;
+    const int irow = o.add(out_counts, (size_t)nr * 4);
+    const nbkd_status rc = run_placed(
+        ws, q, m, flags, o, 40,
+        [&](const float *dq, uint64_t, uint64_t nb, void *const *b, hipStream_t st) {
+            return hist_common(t, ws, dq, nb, thr, nr, (uint32_t *)out_at(b, irow), tot, st);
+        }, s);
     if (rc) return rc;
     if (out_total) {
         static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
@@ -2197,32 +1774,19 @@ nbkd_status query_ball_hist(const Tree &t, const float *q, uint64_t m, const flo
     return NBKD_OK;
 }
 
-// the anisotropic pair counts of m device queries, added to the device
-// counters tot
-static nbkd_status hist2_common(const Tree &t, Workspace &ws, const float *q, uint64_t m,
+// device in: the anisotropic pair counts of m device queries dq, added to the
+// device counters tot
+static nbkd_status hist2_common(const Tree &t, Workspace &ws, const float *dq, uint64_t m,
                                 const Hist2Thr &thr, const Hist2Par &par,
-                                unsigned long long *tot, uint32_t flags, hipStream_t s) {
+                                unsigned long long *tot, hipStream_t s) {
     if (m == 0) return NBKD_OK;
     const uint32_t mm = (uint32_t)m;
-    const float *dq = nullptr;
-    nbkd_status rc = stage_queries(ws, q, m, flags, dq, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, dq, mm, true, p, s);
     if (rc) return rc;
-    uint32_t *ord = nullptr;
-    rc = self_query(t, q, m, flags) ? self_order(t, ws, mm, ord, s)
-                                    : sort_queries(t, ws, dq, mm, ord, s);
-    if (rc) return rc;
-    // periodic queries outside [0, L]^3: listed (the length stays in device
-    // memory), every point tested for them
-    uint32_t *list = nullptr;
-    if (t.periodic) {
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)mm * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + mm, 0, 4, s));
-        outside_box_kernel<<<(mm + TB - 1) / TB, TB, 0, s>>>(dq, mm, t.box, list, list + mm);
-    }
     TimedScope ts(par.los == HIST2_LOS_OBS ? "ball_hist2_obs" : "ball_hist2", s);
-    launch_ball_hist2(t, dq, ord, mm, thr, par, tot, s);
-    if (list) launch_ball_hist2_outside_dev(t, dq, list, list + mm, thr, par, tot, s);
+    launch_ball_hist2(t, dq, p.order, mm, thr, par, tot, s);
+    if (p.list) launch_ball_hist2_outside_dev(t, dq, p.list, p.count, thr, par, tot, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
@@ -2265,17 +1829,11 @@ static nbkd_status hist2_call(const Tree &t, const float *q, uint64_t m, int mod
     NBKD_HIP(hipMemsetAsync(tot, 0, nbins * 8, s));
     // nothing leaves the device but the totals
     flags |= NBKD_OUTPUT_DEVICE;
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
-    nbkd_status rc;
-    if ((flags & dev_io) == dev_io) {
-        rc = hist2_common(t, ws, q, m, thr, par, tot, flags, s);
-    } else {
-        rc = host_pipeline(ws, q, m, flags, 0, nullptr, nullptr, 40,
-                           [&](const float *dq, uint64_t nb, void *const *, hipStream_t st) {
-                               return hist2_common(t, ws, dq, nb, thr, par, tot, flags | dev_io,
-                                                   st);
-                           }, s);
-    }
+    const nbkd_status rc = run_placed(
+        ws, q, m, flags, OutList(), 40,
+        [&](const float *dq, uint64_t, uint64_t nb, void *const *, hipStream_t st) {
+            return hist2_common(t, ws, dq, nb, thr, par, tot, st);
+        }, s);
     if (rc) return rc;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
     NBKD_HIP(hipMemcpyAsync(out_total, tot, nbins * 8, hipMemcpyDeviceToHost, s));
@@ -2303,24 +1861,19 @@ namespace {
 // offsets doff (nb + 1, relative to the batch), ids into di
 nbkd_status ball_fill_batch(const Tree &t, Workspace &ws, const float *dq, uint32_t nb, float r,
                             const uint64_t *doff, uint32_t *di, hipStream_t s) {
-    uint32_t *ord = nullptr;
-    nbkd_status rc = self_query(t, dq, nb, NBKD_INPUT_DEVICE) ? self_order(t, ws, nb, ord, s)
-                                                               : sort_queries(t, ws, dq, nb, ord, s);
+    QueryPlan p;
+    const nbkd_status rc = plan_queries(t, ws, dq, nb, true, p, s);
     if (rc) return rc;
     const float r2 = radius_thr(r);
-    uint32_t *list = nullptr, nout = 0;
-    if (t.periodic) { // periodic queries outside [0, L]^3: every point tested for them
-        list = (uint32_t *)ws.get(WS_LIST, (size_t)nb * 8 + 16, s);
-        if (!list) return NBKD_ENOMEM;
-        NBKD_HIP(hipMemsetAsync(list + nb, 0, 4, s));
-        outside_box_kernel<<<(nb + TB - 1) / TB, TB, 0, s>>>(dq, nb, t.box, list, list + nb);
-        NBKD_HIP(hipMemcpyAsync(&nout, list + nb, 4, hipMemcpyDeviceToHost, s));
+    uint32_t nout = 0; // the fill of the outside queries is sized on the host
+    if (p.list) {
+        NBKD_HIP(hipMemcpyAsync(&nout, p.count, 4, hipMemcpyDeviceToHost, s));
         NBKD_HIP(hipStreamSynchronize(s));
     }
     TimedScope ts("ball_fill", s);
-    launch_ball_packet(t, dq, ord, nb, r2, nullptr, doff, di, nullptr, s);
-    launch_ball_outside(t, dq, list, nout, r2, nullptr, list ? list + nb + 4 : nullptr, doff, di,
-                        s);
+    launch_ball_packet(t, dq, p.order, nb, r2, nullptr, doff, di, nullptr, s);
+    launch_ball_outside(t, dq, p.list, nout, r2, nullptr, p.list ? p.list + nb + 4 : nullptr, doff,
+                        di, s);
     NBKD_HIP(hipGetLastError());
     return NBKD_OK;
 }
@@ -2393,20 +1946,19 @@ nbkd_status query_ball_csr(const Tree &t, const float *q, uint64_t m, float r, u
     Workspace &ws = acquire_ws(t);
     WsCall call(ws, s, std::adopt_lock);
     NBKD_HIP(call.err);
-    const uint32_t dev_io = NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE;
     const bool out_dev = (flags & NBKD_OUTPUT_DEVICE) != 0;
     const uint32_t cflags = flags & (NBKD_INPUT_DEVICE | NBKD_OUTPUT_DEVICE);
     nbkd_status rc;
     {
         // 1. every query's count, streamed into host memory
         std::vector<uint32_t> hc(m);
-        const size_t ob[1] = {4};
-        void *const outs[1] = {hc.data()};
-        rc = host_pipeline(ws, q, m, cflags & ~NBKD_OUTPUT_DEVICE, 1, ob, outs, 40,
-                           [&](const float *dq, uint64_t nb, void *const *o, hipStream_t st) {
-                               return ball_common(t, ws, dq, nb, r, (uint32_t *)o[0],
-                                                  cflags | dev_io, st);
-                           }, s);
+        OutList o;
+        o.add(hc.data(), 4);
+        rc = run_placed(ws, q, m, cflags & ~NBKD_OUTPUT_DEVICE, o, 40,
+                        [&](const float *dq, uint64_t, uint64_t nb, void *const *b,
+                            hipStream_t st) {
+                            return ball_common(t, ws, dq, nb, r, (uint32_t *)b[0], st);
+                        }, s);
         if (rc) return rc;
         offsets[0] = 0;
         for (uint64_t i = 0; i < m; ++i) offsets[i + 1] = offsets[i] + hc[i];
