@@ -34,7 +34,6 @@ using namespace dev;
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // one staged chunk per leaf up to leafsize 64
 
 struct alignas(16) BallLds {
     float4 p4[CHUNK]; // the staged points: x, y, z, original id bits (Tree::p4)
@@ -69,10 +68,7 @@ __device__ __forceinline__ void ball_fill_walk(const DevTree &t, const uint32_t 
         const bool part = need && !full;
         for (uint32_t c0 = lpos; c0 < lend; c0 += CHUNK) {
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
-            wave_sync();
-            glds_f4(t.p4 + c0, W.p4, lane, cn);
-            wait_vm0();
-            wave_sync();
+            stage_points(t.p4, c0, W.p4, lane, cn);
             if (full) {
 #pragma unroll 1
                 for (uint32_t u = 0; u < cn; ++u)
@@ -102,21 +98,14 @@ ball_fill_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     BallLds &W = Wl[wave];
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
-    const bool valid = gq < m;
-    const uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
     const float L = t.box;
-    const bool inside =
-        !PER || (qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f && qz <= L);
-    const bool active = valid && inside;
+    const PacketQuery p = packet_query<PER>(q, order, gq, m, L);
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const bool active = p.valid && p.inside;
     const float thr = active ? r2 : -INFINITY;
-    const uint64_t wpos = active ? row_offsets[qo] : 0;
+    const uint64_t wpos = active ? row_offsets[p.qo] : 0;
     // every active lane's ball clears the box faces: the plain formulas
-    bool plain = false;
-    if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
-    if (plain)
+    if (packet_plain<PER>(active, r2, qx, qy, qz, L))
         ball_fill_walk<PER, false>(t, linfo, pad, out_idx, W, lane, qx, qy, qz, thr, wpos);
     else
         ball_fill_walk<PER, PER>(t, linfo, pad, out_idx, W, lane, qx, qy, qz, thr, wpos);
@@ -543,7 +532,6 @@ ball_count2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *_
 // every point is tested.  Grid: x = point tiles, y = listed query.  Counts
 // accumulate with atomics into out_count (zeroed first); a fill appends at
 // row_offsets[q] + atomicAdd(fill[j]) (rows are sets).
-constexpr int BR_ITEMS = 8;
 __global__ void __launch_bounds__(TB)
 ball_brute_kernel(DevTree t, const float *__restrict__ q, const uint32_t *__restrict__ list,
                   float r2, uint32_t *__restrict__ out_count, uint32_t *__restrict__ fill,
@@ -593,19 +581,16 @@ ball_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *__
     const uint64_t total = (uint64_t)__builtin_amdgcn_readfirstlane(*nout) * ntiles;
     const float L = t.box;
     for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const uint32_t j = (uint32_t)(w / ntiles), tile = (uint32_t)(w - (uint64_t)j * ntiles);
-        const uint32_t qo = list[j];
-        const float qx = q[3 * (size_t)qo], qy = q[3 * (size_t)qo + 1], qz = q[3 * (size_t)qo + 2];
+        const BruteTile b = brute_tile<TB>(w, ntiles, list, q);
         uint32_t c = 0;
-        const uint32_t base = tile * (uint32_t)(TB * BR_ITEMS) + threadIdx.x;
 #pragma unroll
         for (int u = 0; u < BR_ITEMS; ++u) {
-            const uint32_t p = base + u * TB;
-            if (p < t.n8 && point_d2<true>(qx, qy, qz, t.x[p], t.y[p], t.z[p], L) <= r2) ++c;
+            const uint32_t p = b.base + u * TB;
+            if (p < t.n8 && point_d2<true>(b.qx, b.qy, b.qz, t.x[p], t.y[p], t.z[p], L) <= r2) ++c;
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&out_count[qo], c);
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&out_count[b.qo], c);
     }
 }
 

@@ -4,8 +4,9 @@
 // the same d2 and the same test as the single-radius count, so column j equals
 // nbkd_query_ball_count(q, r[j]) bit for bit.
 //
-// 64-query packets, one query per lane, on the shared packet walk (packet.hpp)
-// with the bound t[nr-1].  Each lane keeps a differential histogram in LDS,
+// 64-query packets, one query per lane, behind the shared prologue and on the
+// shared packet walk (packet.hpp packet_query, packet_plain, walk_next_leaf,
+// stage_points) with the bound t[nr-1].  Each lane keeps a differential histogram in LDS,
 // hist[bin][lane] (64 four-byte banks: the wave's accesses to one bin never
 // conflict): a point goes to bin j = the number of thresholds below its d2,
 // points beyond t[nr-1] to a dump row nr that nothing reads.  At a leaf a lane
@@ -31,7 +32,6 @@ using namespace dev;
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // one staged chunk per leaf up to leafsize 64
 constexpr int EV = 8;     // staged points evaluated per step of the threshold loop
 
 // one wave's LDS: the staged points, hist[(nr + 1)][64], the thresholds
@@ -122,10 +122,7 @@ __device__ __forceinline__ void ball_hist_walk(const DevTree &t, const uint32_t 
         const bool plain_leaf = !M || __all(!ev || wrap_free(qx, qy, qz, tb, L));
         for (uint32_t c0 = lpos; c0 < lend; c0 += CHUNK) {
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
-            wave_sync();
-            glds_f4(t.p4 + c0, p4s, lane, cn);
-            wait_vm0();
-            wave_sync();
+            stage_points(t.p4, c0, p4s, lane, cn);
             if (plain_leaf)
                 hist_chunk<false>(p4s, cn, hist, thr, tmask, base, ev, lane, qx, qy, qz, L);
             else
@@ -149,22 +146,16 @@ ball_hist_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__r
     for (int j = 0; j <= nr; ++j) hist[j * 64 + lane] = 0;
     wave_sync();
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
-    const bool valid = gq < m;
-    const uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
     const float L = t.box;
-    const bool inside =
-        !PER || (qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f && qz <= L);
-    const bool active = valid && inside;
+    const PacketQuery p = packet_query<PER>(q, order, gq, m, L);
+    const uint32_t qo = p.qo;
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const bool active = p.valid && p.inside;
     const float r2 = unif(thr[nr - 1]);
     const float kth = active ? r2 : -INFINITY;
     // every active lane's ball of the largest radius clears the box faces:
     // the plain formulas
-    bool plain = false;
-    if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
-    if (plain)
+    if (packet_plain<PER>(active, r2, qx, qy, qz, L))
         ball_hist_walk<PER, false>(t, linfo, pad, p4s, hist, thr, nr, lane, qx, qy, qz, kth);
     else
         ball_hist_walk<PER, PER>(t, linfo, pad, p4s, hist, thr, nr, lane, qx, qy, qz, kth);
@@ -187,8 +178,6 @@ ball_hist_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__r
 // in device memory): every point tested with the reference-exact metric, as in
 // ball_brute_dev_kernel; the cumulative count at threshold j is counted
 // directly.  Rows and totals accumulate with atomics (rows zeroed first).
-constexpr int BR_ITEMS = 8;
-
 __global__ void __launch_bounds__(TB)
 hist_zero_dev_kernel(const uint32_t *__restrict__ list, const uint32_t *__restrict__ nout, int nr,
                      uint32_t *__restrict__ out_counts) {
@@ -210,15 +199,13 @@ hist_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *__
     const uint64_t total = (uint64_t)__builtin_amdgcn_readfirstlane(*nout) * ntiles;
     const float L = t.box;
     for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const uint32_t j = (uint32_t)(w / ntiles), tile = (uint32_t)(w - (uint64_t)j * ntiles);
-        const uint32_t qo = list[j];
-        const float qx = q[3 * (size_t)qo], qy = q[3 * (size_t)qo + 1], qz = q[3 * (size_t)qo + 2];
-        const uint32_t base = tile * (uint32_t)(TB * BR_ITEMS) + threadIdx.x;
+        const BruteTile b = brute_tile<TB>(w, ntiles, list, q);
+        const uint32_t qo = b.qo;
         float d[BR_ITEMS];
 #pragma unroll
         for (int u = 0; u < BR_ITEMS; ++u) {
-            const uint32_t p = base + u * TB;
-            d[u] = p < t.n8 ? point_d2<true>(qx, qy, qz, t.x[p], t.y[p], t.z[p], L) : INFINITY;
+            const uint32_t p = b.base + u * TB;
+            d[u] = p < t.n8 ? point_d2<true>(b.qx, b.qy, b.qz, t.x[p], t.y[p], t.z[p], L) : INFINITY;
         }
         for (int k = 0; k < nr; ++k) {
             const float tk = thr[wave][k];

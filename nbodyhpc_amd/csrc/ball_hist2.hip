@@ -61,7 +61,6 @@ using namespace dev;
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // points staged per step
 constexpr int EV = 4;     // staged points evaluated per step of the threshold loops
 // T1, T2 and the ids of the padded leaves (in LDS, not in NBKD_PAD_LEAVES SGPRs:
 // with them the periodic instances spilled scalar registers)
@@ -296,10 +295,7 @@ __device__ __forceinline__ void hist2_walk(const DevTree &t, const uint32_t *__r
         const bool plain_leaf = !M || __all(!ev || wrap_free(qx, qy, qz, tb, L));
         for (uint32_t c0 = lpos; c0 < lend; c0 += CHUNK) {
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
-            wave_sync();
-            glds_f4(t.p4 + c0, p4s, lane, cn);
-            wait_vm0();
-            wave_sync();
+            stage_points(t.p4, c0, p4s, lane, cn);
             if (plain_leaf)
                 hist2_chunk<false, MODE, LOS>(p4s, cn, c, k0, k1, l0, l1, ev, copy, qx, qy, qz, L,
                                               o);
@@ -330,6 +326,9 @@ ball_hist2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__
     wave_sync();
     const Hist2Ctx c{hist, thr1, thr2, padl, totals, P.n1, P.n2, P.rshift, P.flush_visits};
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
+    // (packet.hpp packet_query written out: through the helper the periodic
+    // instances take other SGPRs and the 16 x 40 (rp, pi) case ran 0.25 % slower,
+    // profiles/r12a_radius_helpers_ab.txt)
     const bool valid = gq < m;
     const uint32_t qo = valid ? order[gq] : 0u;
     const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
@@ -345,8 +344,7 @@ ball_hist2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__
     // every active lane's ball of the bound clears the box faces: the plain
     // formulas (the per-axis squares are then the periodic ones' bits for every
     // point inside the ball, and a point outside it is in no bin either way)
-    bool plain = false;
-    if constexpr (PER) plain = __all(!active || ball_clears_faces(r2, qx, qy, qz, L));
+    const bool plain = packet_plain<PER>(active, r2, qx, qy, qz, L);
     // (read by the observer-frame instances only)
     const Hist2Obs o{P.obs[0], P.obs[1], P.obs[2], qx - P.obs[0], qy - P.obs[1], qz - P.obs[2]};
     if (plain)
@@ -360,8 +358,6 @@ ball_hist2_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__
 // in device memory): every point tested with the reference-exact three-image
 // squares (point_axes<true>), as hist_brute_dev_kernel does; each pair in a bin
 // adds to the totals directly.
-constexpr int BR_ITEMS = 8;
-
 template <int MODE, int LOS>
 __global__ void __launch_bounds__(TB)
 hist2_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *__restrict__ list,
@@ -374,15 +370,12 @@ hist2_brute_dev_kernel(DevTree t, const float *__restrict__ q, const uint32_t *_
     const uint64_t total = (uint64_t)__builtin_amdgcn_readfirstlane(*nout) * ntiles;
     const float L = t.box;
     for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const uint32_t j = (uint32_t)(w / ntiles), tile = (uint32_t)(w - (uint64_t)j * ntiles);
-        const uint32_t qo = list[j];
-        const float qx = q[3 * (size_t)qo], qy = q[3 * (size_t)qo + 1], qz = q[3 * (size_t)qo + 2];
-        const uint32_t base = tile * (uint32_t)(TB * BR_ITEMS) + threadIdx.x;
+        const BruteTile b = brute_tile<TB>(w, ntiles, list, q);
         for (int u = 0; u < BR_ITEMS; ++u) {
-            const uint32_t p = base + u * TB;
+            const uint32_t p = b.base + u * TB;
             if (p >= t.n8) continue;
             float ax, ay, az, x1, pi2;
-            point_axes<true>(qx, qy, qz, t.x[p], t.y[p], t.z[p], L, ax, ay, az);
+            point_axes<true>(b.qx, b.qy, b.qz, t.x[p], t.y[p], t.z[p], L, ax, ay, az);
             hist2_coords<MODE, LOS>(ax, ay, az, x1, pi2);
             // (padding points: x1 is infinite, b1 == n1)
             uint32_t b1 = 0, b2 = 0;
@@ -445,61 +438,30 @@ void launch_ball_hist2(const Tree &t, const float *q, const uint32_t *order, uin
     const uint32_t words = (uint32_t)(par.n1 * par.n2) << par.rshift;
     // (one block shape: 4 waves of at most 8 KiB of histogram, 38 KiB in all)
     const size_t lds = (size_t)WPB * hist2_wave_bytes(words);
-    const bool smu = par.mode == NBKD_HIST2_SMU;
-#define NBKD_H2_LAUNCH(PERV, MODEV, LOSV)                                                          \
-    ball_hist2_kernel<PERV, MODEV, LOSV><<<blocks, TB, lds, s>>>(view(t), t.leafinfo, q, order, m, \
-                                                                 thr, par, pad, totals)
-#define NBKD_H2_LOS(PERV, MODEV)                                                                   \
-    do {                                                                                           \
-        if (par.los == 0)                                                                          \
-            NBKD_H2_LAUNCH(PERV, MODEV, 0);                                                        \
-        else if (par.los == 1)                                                                     \
-            NBKD_H2_LAUNCH(PERV, MODEV, 1);                                                        \
-        else                                                                                       \
-            NBKD_H2_LAUNCH(PERV, MODEV, 2);                                                        \
-    } while (0)
-    if (par.los == HIST2_LOS_OBS) { // (non-periodic trees only: checked by the C entry point)
-        if (smu)
-            NBKD_H2_LAUNCH(false, NBKD_HIST2_SMU, HIST2_LOS_OBS);
+    const auto launch = [&](auto PERV, auto MODE, auto LOS) {
+        ball_hist2_kernel<PERV() != 0, MODE(), LOS()><<<blocks, TB, lds, s>>>(
+            view(t), t.leafinfo, q, order, m, thr, par, pad, totals);
+    };
+    with_constant<NBKD_HIST2_SMU, NBKD_HIST2_RPPI>(par.mode, [&](auto MODE) {
+        if (par.los == HIST2_LOS_OBS) // (non-periodic trees only: checked by the C entry point)
+            launch(std::false_type{}, MODE, std::integral_constant<int, HIST2_LOS_OBS>{});
         else
-            NBKD_H2_LAUNCH(false, NBKD_HIST2_RPPI, HIST2_LOS_OBS);
-    } else if (t.periodic) {
-        if (smu)
-            NBKD_H2_LOS(true, NBKD_HIST2_SMU);
-        else
-            NBKD_H2_LOS(true, NBKD_HIST2_RPPI);
-    } else {
-        if (smu)
-            NBKD_H2_LOS(false, NBKD_HIST2_SMU);
-        else
-            NBKD_H2_LOS(false, NBKD_HIST2_RPPI);
-    }
-#undef NBKD_H2_LOS
-#undef NBKD_H2_LAUNCH
+            with_constant<0, 1, 2>(par.los, [&](auto LOS) {
+                with_constant<1, 0>(t.periodic, [&](auto PERV) { launch(PERV, MODE, LOS); });
+            });
+    });
 }
 
 void launch_ball_hist2_outside_dev(const Tree &t, const float *q, const uint32_t *list,
                                    const uint32_t *nout, const Hist2Thr &thr, Hist2Par par,
                                    unsigned long long *totals, hipStream_t s) {
     const uint32_t ntiles = (uint32_t)((t.n8 + TB * BR_ITEMS - 1) / (TB * BR_ITEMS));
-#define NBKD_H2_BRUTE(MODEV, LOSV)                                                                 \
-    hist2_brute_dev_kernel<MODEV, LOSV><<<2048, TB, 0, s>>>(view(t), q, list, nout, ntiles, thr,   \
-                                                            par, totals)
-#define NBKD_H2_BRUTE_LOS(MODEV)                                                                   \
-    do {                                                                                           \
-        if (par.los == 0)                                                                          \
-            NBKD_H2_BRUTE(MODEV, 0);                                                               \
-        else if (par.los == 1)                                                                     \
-            NBKD_H2_BRUTE(MODEV, 1);                                                               \
-        else                                                                                       \
-            NBKD_H2_BRUTE(MODEV, 2);                                                               \
-    } while (0)
-    if (par.mode == NBKD_HIST2_SMU)
-        NBKD_H2_BRUTE_LOS(NBKD_HIST2_SMU);
-    else
-        NBKD_H2_BRUTE_LOS(NBKD_HIST2_RPPI);
-#undef NBKD_H2_BRUTE_LOS
-#undef NBKD_H2_BRUTE
+    with_constant<NBKD_HIST2_SMU, NBKD_HIST2_RPPI>(par.mode, [&](auto MODE) {
+        with_constant<0, 1, 2>(par.los, [&](auto LOS) {
+            hist2_brute_dev_kernel<MODE(), LOS()><<<2048, TB, 0, s>>>(view(t), q, list, nout, ntiles,
+                                                                      thr, par, totals);
+        });
+    });
 }
 
 } // namespace nbkd

@@ -3,8 +3,12 @@
 //   out_sum[i, b, c] = sum_j values[j, c]  over the points j of bin b of query i,
 // bin b = the number of thresholds t_ik = fl(e_ik * e_ik), e_ik = fl(radii[k] *
 // scale[i]), with !(d2(i, j) <= t_ik): ball_hist.hip's binning against each
-// lane's own thresholds, with ball_sum.hip's staged values where the histogram
-// counts.
+// lane's own thresholds, with ball_sum.hip's staged values (packet.hpp
+// stage_values) where the histogram counts.  The threshold classification of a
+// leaf and the binning step of a chunk are ball_hist.hip's statements with the
+// lane's own thresholds (thr[j * 64 + lane] for thr[j]); they are written out
+// in both files: as shared functions they compile to other loop bodies here
+// (DESIGN.md section 3).
 //
 // ball_profile_kernel: 64-query packets, one wave each, the packet walk
 // (packet.hpp, the macro form NBKD_GWALK) with the lane's own bound t_i,nr-1.  Per wave in LDS: the staged
@@ -42,7 +46,6 @@ namespace {
 using namespace dev;
 
 constexpr int TBMAX = 256;
-constexpr int CHUNK = 64; // staged points per step (a leaf of 65..128 points takes two)
 constexpr int EV = 8;     // staged points binned per step of the threshold loop
 constexpr uint32_t LDS_BLOCK = 64u * 1024u;
 
@@ -178,8 +181,8 @@ __device__ __forceinline__ void ball_profile_walk(const DevTree &t,
         uint32_t lpos = 0, lend = 0;
         NBKD_GWALK(found, lpos, lend);
         if (!found) break;
-        const NodeBox lb_ = ((cbox_ptr)linfo)[node];
-        const float tb[6] = {lb_.b[0], lb_.b[3], lb_.b[1], lb_.b[4], lb_.b[2], lb_.b[5]};
+        float tb[6];
+        leaf_tight_box(linfo, node, tb);
         const float lb = box_lb2<M>(qx, qy, qz, tb, L);
         const bool need = lb <= kth;
         if (!__any(need)) continue;
@@ -213,17 +216,7 @@ __device__ __forceinline__ void ball_profile_walk(const DevTree &t,
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
             wave_sync();
             if (tmask) glds_f4(t.p4 + c0, p4s, lane, cn);
-            if constexpr (NV == 4) {
-                glds_f4(reinterpret_cast<const float4 *>(vt) + c0, reinterpret_cast<float4 *>(vs),
-                        lane, cn);
-            } else {
-                // the chunk's cn * NV consecutive floats of vt, 64 per load
-                const uint32_t nf = cn * NV;
-#pragma unroll
-                for (int c = 0; c < NV; ++c)
-                    glds_f32(vt + (size_t)c0 * NV + c * 64, vs + c * 64, lane,
-                             nf > (uint32_t)c * 64u ? nf - (uint32_t)c * 64u : 0u);
-            }
+            stage_values<NV>(vt, c0, vs, lane, cn);
             wait_vm0();
             wave_sync();
             if (full) {
@@ -265,15 +258,11 @@ ball_profile_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *
     float *const acc = vs + CHUNK * NV;
     float *const thr = acc + (nr + 1) * NV * 64;
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * wpb + wave) * 64u + lane;
-    const bool valid = gq < m;
-    uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
-    const float sc = (valid && scale) ? scale[qo] : 1.0f;
     const float L = t.box;
-    const bool inside =
-        !PER || (qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f && qz <= L);
+    const PacketQuery p = packet_query<PER>(q, order, gq, m, L);
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const bool valid = p.valid, inside = p.inside;
+    const float sc = (valid && scale) ? scale[p.qo] : 1.0f;
     // a lane without a query, outside the box or with a NaN, infinite or
     // negative scale walks nothing: every threshold and the bound are -inf
     const bool ok = valid && inside && scale_ok(sc);
@@ -289,13 +278,7 @@ ball_profile_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *
     // periodic ones' bits for every point within it and fail the test for every
     // point beyond (ball.hip ball_fill_kernel), so the packet walks and tests
     // with them
-    bool plain = false;
-    if constexpr (PER) {
-        const float r1 = sqrtf(fmaxf(kth, 0.0f)) * 1.01f + L * 1e-6f;
-        const bool wf = kth < 0.0f || (r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 &&
-                                       L - qy >= r1 && qz >= r1 && L - qz >= r1);
-        plain = __all(wf);
-    }
+    const bool plain = packet_plain<PER>(!(kth < 0.0f), kth, qx, qy, qz, L);
     if (plain)
         ball_profile_walk<PER, false, NV>(t, linfo, pad, vt, p4s, vs, acc, thr, nr, lane, qx, qy,
                                           qz, kth);
@@ -307,7 +290,7 @@ ball_profile_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *
     // periodic query outside the box is the brute kernel's.  (The id again: not
     // kept live through the walk.)
     if (valid && inside) {
-        qo = order[gq];
+        const uint32_t qo = order[gq];
         float *const row = out_sum + (size_t)qo * (uint32_t)(nr * NV);
         for (int j = 0; j < nr * NV; ++j) row[j] = acc[j * 64 + lane];
     }
@@ -391,12 +374,9 @@ void launch_ball_profile(const Tree &t, const float *q, const float *scale, cons
                          float *out_sum, hipStream_t s) {
     if (m == 0) return;
     const PadLeaves pad = pad_leaves_of(t);
-    switch (nv) {
-    case 1: launch_profile_n<1>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;
-    case 2: launch_profile_n<2>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;
-    case 3: launch_profile_n<3>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;
-    default: launch_profile_n<4>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s); break;
-    }
+    with_constant<1, 2, 3, 4>(nv, [&](auto NV) {
+        launch_profile_n<NV()>(t, q, scale, order, m, R, nr, pad, vt, out_sum, s);
+    });
 }
 
 void launch_ball_profile_outside_dev(const Tree &t, const float *q, const float *scale,

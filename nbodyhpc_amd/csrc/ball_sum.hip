@@ -7,9 +7,10 @@
 //
 // ball_sum_kernel is ball.hip's CSR fill (ball_fill_walk) with a register
 // accumulate where the fill stores an id: 64-query packets, one wave each, the
-// shared packet walk, leaf chunks staged into LDS from Tree::p4 and, beside
-// them, the chunk's rows of the values in tree order (vt, written once per
-// call by ball_sum_gather_kernel); each lane loops over the staged points.
+// shared packet walk behind packet.hpp's prologue (packet_query, packet_plain),
+// leaf chunks staged into LDS from Tree::p4 and, beside them, the chunk's rows
+// of the values in tree order (vt, written once per call by
+// ball_sum_gather_kernel; stage_values); each lane loops over the staged points.
 // Every (query, channel) is summed by one lane into one f32 accumulator in the
 // walk's order: no floating-point atomics, identical calls give identical bits.
 //
@@ -27,7 +28,6 @@ using namespace dev;
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // staged points per step (a leaf of 65..128 points takes two)
 
 // 64 * (16 + 4 NV) bytes per wave
 template <int NV> struct alignas(16) SumLds {
@@ -109,17 +109,7 @@ __device__ __forceinline__ void ball_sum_walk(const DevTree &t, const uint32_t *
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
             wave_sync();
             glds_f4(t.p4 + c0, W.p4, lane, cn);
-            if constexpr (NV == 4) {
-                glds_f4(reinterpret_cast<const float4 *>(vt) + c0,
-                        reinterpret_cast<float4 *>(W.v), lane, cn);
-            } else {
-                // the chunk's cn * NV consecutive floats of vt, 64 per load
-                const uint32_t nf = cn * NV;
-#pragma unroll
-                for (int c = 0; c < NV; ++c)
-                    glds_f32(vt + (size_t)c0 * NV + c * 64, W.v + c * 64, lane,
-                             nf > (uint32_t)c * 64u ? nf - (uint32_t)c * 64u : 0u);
-            }
+            stage_values<NV>(vt, c0, W.v, lane, cn);
             wait_vm0();
             wave_sync();
             if (full) {
@@ -157,21 +147,16 @@ ball_sum_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__re
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     SumLds<NV> &W = Wl[wave];
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
-    const bool valid = gq < m;
-    uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
-    const float hq = valid ? h[qo] : -1.0f;
     const float L = t.box;
-    const bool inside =
-        !PER || (qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f && qz <= L);
+    const PacketQuery p = packet_query<PER>(q, order, gq, m, L);
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const bool valid = p.valid, inside = p.inside;
+    const float hq = valid ? h[p.qo] : -1.0f;
     const float thr = ball_thr(hq, valid && inside);
     const float inv = ball_inv(hq);
     // every lane's own ball clears the box faces (an empty ball clears them
     // too): the plain formulas
-    bool plain = false;
-    if constexpr (PER) plain = __all(thr < 0.0f || ball_clears_faces(thr, qx, qy, qz, L));
+    const bool plain = packet_plain<PER>(!(thr < 0.0f), thr, qx, qy, qz, L);
     float acc[NV];
 #pragma unroll
     for (int c = 0; c < NV; ++c) acc[c] = 0.0f;
@@ -186,7 +171,7 @@ ball_sum_kernel(DevTree t, const uint32_t *__restrict__ linfo, const float *__re
     // the box is the brute kernel's.  (The id again: not kept live through the
     // walk.)
     if (valid && inside) {
-        qo = order[gq];
+        const uint32_t qo = order[gq];
         if (out_sum) {
 #pragma unroll
             for (int c = 0; c < NV; ++c) out_sum[(size_t)qo * NV + c] = acc[c];
@@ -274,18 +259,6 @@ void launch_sum_kn(const Tree &t, const float *q, const float *h, const uint32_t
                                                                pad, vt, out_sum, out_count);
 }
 
-template <int KERN>
-void launch_sum_k(const Tree &t, const float *q, const float *h, const uint32_t *order, uint32_t m,
-                  const PadLeaves &pad, const float *vt, int nv, float *out_sum,
-                  uint32_t *out_count, hipStream_t s) {
-    switch (nv) {
-    case 1: launch_sum_kn<KERN, 1>(t, q, h, order, m, pad, vt, out_sum, out_count, s); break;
-    case 2: launch_sum_kn<KERN, 2>(t, q, h, order, m, pad, vt, out_sum, out_count, s); break;
-    case 3: launch_sum_kn<KERN, 3>(t, q, h, order, m, pad, vt, out_sum, out_count, s); break;
-    default: launch_sum_kn<KERN, 4>(t, q, h, order, m, pad, vt, out_sum, out_count, s); break;
-    }
-}
-
 } // namespace
 
 void launch_ball_sum_gather(const Tree &t, const float *values, int nv, float *vt, hipStream_t s) {
@@ -301,12 +274,11 @@ void launch_ball_sum(const Tree &t, const float *q, const float *h, const uint32
                      uint32_t *out_count, hipStream_t s) {
     if (m == 0) return;
     const PadLeaves pad = pad_leaves_of(t);
-    if (kernel == NBKD_KERNEL_TOPHAT)
-        launch_sum_k<NBKD_KERNEL_TOPHAT>(t, q, h, order, m, pad, vt, nv, out_sum, out_count, s);
-    else if (kernel == NBKD_KERNEL_CUBIC)
-        launch_sum_k<NBKD_KERNEL_CUBIC>(t, q, h, order, m, pad, vt, nv, out_sum, out_count, s);
-    else
-        launch_sum_k<NBKD_KERNEL_WENDLAND>(t, q, h, order, m, pad, vt, nv, out_sum, out_count, s);
+    with_constant<NBKD_KERNEL_TOPHAT, NBKD_KERNEL_CUBIC, NBKD_KERNEL_WENDLAND>(kernel, [&](auto K) {
+        with_constant<1, 2, 3, 4>(nv, [&](auto NV) {
+            launch_sum_kn<K(), NV()>(t, q, h, order, m, pad, vt, out_sum, out_count, s);
+        });
+    });
 }
 
 void launch_ball_sum_outside_dev(const Tree &t, const float *q, const float *h,

@@ -51,7 +51,6 @@ using namespace dev;
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // one staged chunk per leaf up to leafsize 64
 
 struct alignas(16) FofLds {
     float4 p4[CHUNK]; // the staged points (Tree::p4; .w is not used here)
@@ -144,12 +143,7 @@ __device__ __forceinline__ void fof_hook_walk(const DevTree &t, const uint32_t *
             const uint32_t cn = min((uint32_t)CHUNK, lend - c0);
             // the lane's friends in this chunk are at positions c0 .. c0 + lim - 1 < gq
             const uint32_t lim = gq > c0 ? min(cn, gq - c0) : 0u;
-            if (stage) {
-                wave_sync();
-                glds_f4(t.p4 + c0, W.p4, lane, cn);
-                wait_vm0();
-                wave_sync();
-            }
+            if (stage) stage_points(t.p4, c0, W.p4, lane, cn);
             if (full) {
 #pragma unroll 1
                 for (uint32_t u = 0; u < lim; ++u) rq = fof_unite<HV>(parent, rq, c0 + u);
@@ -187,9 +181,7 @@ fof_hook_kernel(DevTree t, const uint32_t *__restrict__ linfo, const uint32_t *_
     const float L = t.box;
     const float thr = active ? b2 : -INFINITY;
     // every active lane's ball clears the box faces: the plain formulas
-    bool plain = false;
-    if constexpr (PER) plain = __all(!active || ball_clears_faces(b2, qx, qy, qz, L));
-    if (plain)
+    if (packet_plain<PER>(active, b2, qx, qy, qz, L))
         fof_hook_walk<PER, false, HV>(t, linfo, pad, parent, W, lane, gq, qx, qy, qz, thr);
     else
         fof_hook_walk<PER, PER, HV>(t, linfo, pad, parent, W, lane, gq, qx, qy, qz, thr);

@@ -147,11 +147,9 @@ gravity_walk_kernel(DevTree t, const GravRec *__restrict__ rec, const float *__r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     GravLds &W = Wl[wave];
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
-    const bool valid = gq < m;
-    uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
+    const PacketQuery p = packet_query<false>(q, order, gq, m, 0.0f);
+    const float qx = p.x, qy = p.y, qz = p.z;
+    const bool valid = p.valid;
     const cnode_ptr cnodes = (cnode_ptr)t.nodes;
     const crec_ptr crec = (crec_ptr)rec;
     const bool open_all = !(th2 > 0.0f); // theta = 0: the direct sum
@@ -215,7 +213,7 @@ gravity_walk_kernel(DevTree t, const GravRec *__restrict__ rec, const float *__r
     }
     // (the id again: not kept live through the walk)
     if (valid) {
-        qo = order[gq];
+        const uint32_t qo = order[gq];
         if (out_phi) out_phi[qo] = phi;
         if (out_acc) {
             out_acc[3 * (size_t)qo] = ax;

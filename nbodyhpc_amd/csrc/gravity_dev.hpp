@@ -12,7 +12,7 @@ namespace grav {
 
 constexpr int TB = 256;
 constexpr int WPB = TB / 64;
-constexpr int CHUNK = 64; // staged points per step (a leaf of 65..128 points takes two)
+using dev::CHUNK;
 
 // 64 * 20 bytes per wave
 struct alignas(16) GravLds {

@@ -228,11 +228,14 @@ gravity_ewald_walk_kernel(DevTree t, const GravRec *__restrict__ rec, const floa
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     GravLds &W = Wl[wave];
     const uint32_t gq = (xcd_block(blockIdx.x, gridDim.x) * WPB + wave) * 64u + lane;
+    // (packet.hpp packet_query written out: through the helper the compares
+    // come out in another order and the walk ran 0.85 % slower,
+    // profiles/r12a_radius_helpers_ab.txt)
     const bool valid = gq < m;
-    uint32_t qo = valid ? order[gq] : 0u;
-    const float qx = valid ? q[3 * (size_t)qo] : 0.0f;
-    const float qy = valid ? q[3 * (size_t)qo + 1] : 0.0f;
-    const float qz = valid ? q[3 * (size_t)qo + 2] : 0.0f;
+    const uint32_t qo0 = valid ? order[gq] : 0u;
+    const float qx = valid ? q[3 * (size_t)qo0] : 0.0f;
+    const float qy = valid ? q[3 * (size_t)qo0 + 1] : 0.0f;
+    const float qz = valid ? q[3 * (size_t)qo0 + 2] : 0.0f;
     const float L = E.L;
     // a query outside [0, L]^3 (or NaN) takes no part in the walk
     const bool inside = valid && qx >= 0.0f && qx <= L && qy >= 0.0f && qy <= L && qz >= 0.0f &&
@@ -302,7 +305,7 @@ gravity_ewald_walk_kernel(DevTree t, const GravRec *__restrict__ rec, const floa
     }
     // (the id again: not kept live through the walk)
     if (valid) {
-        qo = order[gq];
+        const uint32_t qo = order[gq];
         if (!inside) phi = ax = ay = az = __builtin_nanf("");
         if (out_phi) out_phi[qo] = phi;
         if (out_acc) {

@@ -9,6 +9,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nbkd.h"
@@ -226,6 +227,20 @@ struct DevTree {
 inline DevTree view(const Tree &t) {
     return DevTree{t.x, t.y, t.z, t.idx, t.p4, t.nodes, (uint32_t)t.n8, (uint32_t)t.nnodes, t.box,
                    t.nbox};
+}
+
+// A launcher's run-time value as a compile-time constant, for the kernels'
+// template arguments: f(std::integral_constant<int, V>{}) for the first V of
+// the list that equals v, for the last one when none does.
+template <int V, int... Vs, class F> inline void with_constant(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) {
+        f(std::integral_constant<int, V>{});
+    } else {
+        if (v == V)
+            f(std::integral_constant<int, V>{});
+        else
+            with_constant<Vs...>(v, f);
+    }
 }
 
 // Tuning.  The production library reads no environment variable: every

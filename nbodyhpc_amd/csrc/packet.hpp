@@ -1,10 +1,14 @@
 // Device helpers shared by the packet kernels (knn_collect.hip, ball.hip,
-// ball_hist.hip, ball_sum.hip, ball_profile.hip, fof.hip): direct-to-LDS loads,
-// wave-local sync, the scalar-cache view of the node table, LDS-staged row
-// stores and the fallback listing, the per-leaf idioms of the radius kernels
-// (tight box, padding leaves, the plain-packet test), and the packet walk
-// (walk_begin / walk_next_leaf; the kNN collect's hand-scheduled descent; the
-// macro form ball_profile.hip keeps).
+// ball_hist.hip, ball_hist2.hip, ball_sum.hip, ball_profile.hip, fof.hip, the
+// gravity walks): direct-to-LDS loads, wave-local sync and the staging of a
+// leaf chunk's points and value rows (stage_points, stage_values), the
+// scalar-cache view of the node table, LDS-staged row stores and the fallback
+// listing, what a radius kernel does before its walk (packet_query: the lane's
+// query and whether it is walked; packet_plain: the packet's vote for the plain
+// formulas), the per-leaf idioms (tight box, padding leaves), the head of the
+// brute kernels' work items (brute_tile), and the packet walk (walk_begin /
+// walk_next_leaf; the kNN collect's hand-scheduled descent; the macro form
+// ball_profile.hip keeps).
 #pragma once
 
 #include "metric.hpp"
@@ -30,6 +34,45 @@ __device__ __forceinline__ void glds_f4(const float4 *src, float4 *dst, int lane
 // s_waitcnt vmcnt(0) (expcnt / lgkmcnt untouched): the direct-to-LDS loads have landed
 __device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// points staged per step: one chunk per leaf up to leafsize 64 (a leaf of
+// 65..128 points takes two)
+constexpr int CHUNK = 64;
+
+// the chunk's points p4[c0 .. c0 + cn) into dst (LDS), between two wave syncs:
+// the previous chunk's readers are done before the loads, the loads have
+// landed before the next read
+__device__ __forceinline__ void stage_points(const float4 *p4, uint32_t c0, float4 *dst, int lane,
+                                             uint32_t cn) {
+    wave_sync();
+    glds_f4(p4 + c0, dst, lane, cn);
+    wait_vm0();
+    wave_sync();
+}
+
+// the chunk's NV-channel value rows vt[c0 .. c0 + cn) (tree order) into dst
+// (LDS).  Loads only: the caller issues them after its wave sync, beside the
+// points', and waits once (wait_vm0) before the second sync.
+template <int NV>
+__device__ __forceinline__ void stage_values(const float *vt, uint32_t c0, float *dst, int lane,
+                                             uint32_t cn) {
+    if constexpr (NV == 4) {
+        glds_f4(reinterpret_cast<const float4 *>(vt) + c0, reinterpret_cast<float4 *>(dst), lane,
+                cn);
+    } else {
+        // the chunk's cn * NV consecutive floats of vt, 64 per load
+        const uint32_t nf = cn * NV;
+#pragma unroll
+        for (int c = 0; c < NV; ++c)
+            glds_f32(vt + (size_t)c0 * NV + c * 64, dst + c * 64, lane,
+                     nf > (uint32_t)c * 64u ? nf - (uint32_t)c * 64u : 0u);
+    }
+}
+
 constexpr int pow2_floor(int v) { return v >= 64 ? 64 : v >= 32 ? 32 : v >= 16 ? 16 : v >= 8 ? 8 : 4; }
 constexpr int pow2_ceil(int v) { return v <= 4 ? 4 : v <= 8 ? 8 : v <= 16 ? 16 : v <= 32 ? 32 : 64; }
 
@@ -40,11 +83,6 @@ typedef const __attribute__((address_space(4))) nbkd_node *cnode_ptr;
 #else
 typedef const nbkd_node *cnode_ptr;
 #endif
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // Staged registers j = 0..CC-1 of the 64 lanes (word (j, row) at j*64 + (row ^ j))
 // are output columns c = c0 + j of row `row` (query rowq[row]; 0xFFFFFFFF = no
@@ -131,13 +169,71 @@ __device__ __forceinline__ bool leaf_padded(const PadLeaves &pad, const uint32_t
 // by a margin r' > r.  When that holds for every lane that walks, the plain
 // formulas give the periodic ones' bits for every point within r and fail the
 // test for every point beyond (knn_collect.hip collect_packet), so the packet
-// walks and tests with them.  The caller adds its own guard for the lanes that
-// do not walk, and the vote.
+// walks and tests with them.  packet_plain below adds the guard for the lanes
+// that do not walk, and the vote.
 __device__ __forceinline__ bool ball_clears_faces(const float r2, const float qx, const float qy,
                                                   const float qz, const float L) {
     const float r1 = sqrtf(fmaxf(r2, 0.0f)) * 1.01f + L * 1e-6f;
     return r1 <= 0.25f * L && qx >= r1 && L - qx >= r1 && qy >= r1 && L - qy >= r1 && qz >= r1 &&
            L - qz >= r1;
+}
+
+// One lane's query of a packet: sorted position gq of the m queries is input
+// row qo = order[gq] (a lane past the end holds row 0 at the origin).  inside:
+// the query lies in [0, L]^3, always true on a non-periodic tree; a periodic
+// query outside the box is not walked (its minimum-image pruning is not a
+// bound) and is answered by the kernel family's brute kernel.
+struct PacketQuery {
+    uint32_t qo;
+    float x, y, z;
+    bool valid, inside;
+};
+template <bool PER>
+__device__ __forceinline__ PacketQuery packet_query(const float *q, const uint32_t *order,
+                                                    const uint32_t gq, const uint32_t m,
+                                                    const float L) {
+    PacketQuery p;
+    p.valid = gq < m;
+    p.qo = p.valid ? order[gq] : 0u;
+    p.x = p.valid ? q[3 * (size_t)p.qo] : 0.0f;
+    p.y = p.valid ? q[3 * (size_t)p.qo + 1] : 0.0f;
+    p.z = p.valid ? q[3 * (size_t)p.qo + 2] : 0.0f;
+    p.inside = !PER || (p.x >= 0.0f && p.x <= L && p.y >= 0.0f && p.y <= L && p.z >= 0.0f &&
+                        p.z <= L);
+    return p;
+}
+
+// The packet's vote: every lane that walks (`walks`; a lane without a query,
+// outside the box or with an empty ball does not) has a ball that clears the
+// box faces, so the packet walks and tests with the plain formulas.
+// Wave-uniform; false on a non-periodic tree, whose formulas are plain already.
+template <bool PER>
+__device__ __forceinline__ bool packet_plain(const bool walks, const float r2, const float qx,
+                                             const float qy, const float qz, const float L) {
+    bool plain = false;
+    if constexpr (PER) plain = __all(!walks || ball_clears_faces(r2, qx, qy, qz, L));
+    return plain;
+}
+
+// ------------------------------------------------------------------ brute kernels
+// The kernels that answer the periodic queries outside [0, L]^3 stride over
+// (listed query, point tile) pairs, a tile BR_ITEMS points per thread of the
+// block: work item w is tile w % ntiles of listed query w / ntiles; the thread's
+// points are base + u * TB, u < BR_ITEMS.
+constexpr int BR_ITEMS = 8;
+struct BruteTile {
+    uint32_t qo;
+    float qx, qy, qz;
+    uint32_t base;
+};
+template <int TB>
+__device__ __forceinline__ BruteTile brute_tile(const uint64_t w, const uint32_t ntiles,
+                                                const uint32_t *__restrict__ list,
+                                                const float *__restrict__ q) {
+    const uint32_t j = (uint32_t)(w / ntiles), tile = (uint32_t)(w - (uint64_t)j * ntiles);
+    const uint32_t qo = list[j];
+    return {qo, q[3 * (size_t)qo], q[3 * (size_t)qo + 1], q[3 * (size_t)qo + 2],
+            tile * (uint32_t)(TB * BR_ITEMS) + threadIdx.x};
 }
 
 // ------------------------------------------------------------------ packet walk

@@ -4,7 +4,13 @@ fill (ball.hip), the radius histogram (ball_hist.hip), the kernel-weighted sums
 walk_next_leaf, the radial profiles (ball_profile.hip) on the macro form of the
 same traversal, on the walk shapes their own tests do not reach: split planes
 tied with the queries, a deep stack, plain and periodic packets in one launch,
-and an open tree with queries far outside the data.
+and an open tree with queries far outside the data.  The test_prologue_* cases
+run what the five radius kernels do before the walk (packet_query, packet_plain)
+with a wave and lanes without a query, periodic queries outside the box, a plain
+and a non-plain packet and a padded leaf; the two gravity walks, which have no
+vote, meet those conditions in their own tests
+(test_small_query_counts with m = 1, 63, 65 on 700 points, test_seventeen_points,
+and test_gpu_gravity_ewald.py's test_outside_queries).
 
 Every output is compared with a brute force in plain numpy on the host: the
 f32 distances of tests.parity.d2_ref between the queries and the points, in
@@ -233,6 +239,115 @@ def test_fof_partition(gpu, name):
     assert 1 < ng < len(want)  # neither one group nor none
     assert np.array_equal(lab, want)
     assert np.array_equal(siz, np.bincount(want, minlength=len(want)).astype(np.uint32))
+
+
+# ---------------------------------------------------------------- the packet prologue
+# What the kernels do before the walk (packet.hpp packet_query, packet_plain):
+# lanes and a whole wave without a query, periodic queries outside the box,
+# which go to the brute kernels, one packet that votes for the plain formulas
+# and packets that do not, on a tree with a padded leaf.
+PRO_N, PRO_M, PRO_R = 3001, 131, 0.05
+
+
+@functools.lru_cache(maxsize=None)
+def prologue_case(box):
+    """(points, [first call's queries, second call's], [their d2 matrices]):
+    131 queries, 5 outside [0, 1]^3, 63 within 0.02 of a face, 63 interior, in
+    mixed order; then 64 inside [0.4, 0.6]^3, a single packet that votes plain
+    on the periodic tree."""
+    pts = uniform(PRO_N, 950)
+    rng = np.random.default_rng(951)
+    face = uniform(63, 952)
+    ax, side = rng.integers(0, 3, 63), rng.integers(0, 2, 63)
+    off = rng.uniform(0.0, 0.02, 63).astype(np.float32)
+    face[np.arange(63), ax] = np.where(side == 0, off, np.float32(1.0) - off)
+    inner = (0.2 + 0.6 * uniform(63, 953)).astype(np.float32)
+    out = uniform(5, 954)
+    out[[0, 1, 2], [0, 1, 2]] += np.float32(1.5)
+    out[[3, 4], [2, 0]] = np.float32(-0.3), np.float32(-0.01)
+    q1 = np.concatenate([face, inner, out])[rng.permutation(PRO_M)]
+    q2 = (0.4 + 0.2 * uniform(64, 955)).astype(np.float32)
+    assert len(q1) == PRO_M and PRO_N % 8 != 0
+    assert ((q1 < 0.0) | (q1 > 1.0)).any(axis=1).sum() == 5
+    assert q2.min() >= 0.4 and q2.max() <= 0.6
+    qs = [q1, q2]
+    d2 = [d2_ref(q[:, None, :], pts[None, :, :], box) for q in qs]
+    for a in [pts] + qs + d2:
+        a.setflags(write=False)
+    return pts, qs, d2
+
+
+@pytest.mark.parametrize("box", [None, 1.0], ids=["open", "periodic"])
+def test_prologue_csr_rows(gpu, box):
+    pts, qs, d2s = prologue_case(box)
+    t = gpu.Tree(pts, leafsize=16, boxsize=box)
+    for q, d2 in zip(qs, d2s):
+        inside = d2 <= np.float32(PRO_R) * np.float32(PRO_R)
+        off, idx = t.ball_csr(q, PRO_R, sorted=True)
+        assert np.array_equal(off, np.concatenate([[0], np.cumsum(inside.sum(axis=1))])
+                              .astype(np.uint64))
+        assert np.array_equal(idx, np.nonzero(inside)[1].astype(np.uint32))
+    t.close()
+
+
+@pytest.mark.parametrize("box", [None, 1.0], ids=["open", "periodic"])
+def test_prologue_histogram(gpu, box):
+    pts, qs, d2s = prologue_case(box)
+    radii = radii_of(PRO_R)
+    t = gpu.Tree(pts, leafsize=16, boxsize=box)
+    for q, d2 in zip(qs, d2s):
+        got, _ = t.ball_hist(q, radii, total=False)
+        want = np.stack([(d2 <= rk * rk).sum(axis=1) for rk in radii], axis=1)
+        assert want[:, -1].max() > 0
+        assert np.array_equal(got, want.astype(np.uint32))
+    t.close()
+
+
+@pytest.mark.parametrize("box", [None, 1.0], ids=["open", "periodic"])
+def test_prologue_pair_counts(gpu, box):
+    from tests import aniso_ref as ar
+    pts, qs, _ = prologue_case(box)
+    e1 = np.array([0.01, 0.02, PRO_R], np.float32)
+    t = gpu.Tree(pts, leafsize=16, boxsize=box)
+    for q in qs:
+        for mode, e2, los in ((ar.RPPI, np.array([0.01, PRO_R], np.float32), 2),
+                              (ar.SMU, np.array([0.5, 1.0], np.float32), 0)):
+            want = ar.hist2_ref(pts, q, e1, e2, mode, los, box)
+            assert want.sum() > 0
+            assert np.array_equal(t.ball_hist2(q, e1, e2, mode, los), want)
+    t.close()
+
+
+@pytest.mark.parametrize("box", [None, 1.0], ids=["open", "periodic"])
+def test_prologue_tophat_sum(gpu, box):
+    """Weights 1..8: every sum is an integer below 2^24, exact in any order."""
+    pts, qs, d2s = prologue_case(box)
+    w = np.random.default_rng(956).integers(1, 9, size=PRO_N).astype(np.float32)
+    t = gpu.Tree(pts, leafsize=16, boxsize=box)
+    for q, d2 in zip(qs, d2s):
+        inside = d2 <= np.float32(PRO_R) * np.float32(PRO_R)
+        got, cnt = t.ball_sum(q, np.full(len(q), PRO_R, np.float32), w,
+                              kernel=gpu.KERNEL_TOPHAT, count=True)
+        assert np.array_equal(got.astype(np.float64), inside.astype(np.float64) @ w)
+        assert np.array_equal(cnt, inside.sum(axis=1).astype(np.uint32))
+    t.close()
+
+
+@pytest.mark.parametrize("box", [None, 1.0], ids=["open", "periodic"])
+def test_prologue_profile(gpu, box):
+    pts, qs, d2s = prologue_case(box)
+    w = np.random.default_rng(956).integers(1, 9, size=PRO_N).astype(np.float32)
+    radii = radii_of(PRO_R)
+    t = gpu.Tree(pts, leafsize=16, boxsize=box)
+    for q, d2 in zip(qs, d2s):
+        # bin = the number of thresholds with !(d2 <= t_k); bin NR is outside
+        b = np.zeros(d2.shape, np.int64)
+        for rk in radii:
+            b += ~(d2 <= rk * rk)
+        want = np.stack([(b == k).astype(np.float64) @ w for k in range(NR)], axis=1)
+        assert want.sum() > 0
+        assert np.array_equal(t.ball_profile(q, radii, w).astype(np.float64), want)
+    t.close()
 
 
 # ---------------------------------------------------------------- the order pin
